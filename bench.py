@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: classifier-free-guided 1000-step DDPM sampling of 64x64 images.
 
-    python bench.py --gpus N --steps K --warmup W [--prec f32|f16x3|bf16x3] [--workload c2|c5]
+    python bench.py --gpus N --steps K --warmup W [--prec f32|f16x3|bf16x3] [--workload c2|c5] [--dump-outputs DIR]
 
 A "step" is one CFG sampling step of the reference's native sampler on one batch of synthetic input:
 one UNet evaluation at 2B (cond + uncond) + the fused x0/posterior update (ddpm_sampler.py:154-192).
@@ -541,6 +541,25 @@ def train_step_roofline(model, prec, B, S):
                      "per-step weight re-pack, the optimizer and host gaps that the wall-clock `ms` includes")
 
 
+DUMP_BUDGET = (64 << 20) - (4 << 10)        # 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every non-empty array as <path>/<name>.npy in float32, full shape.  When they would exceed `budget`
+    bytes together, each is written as a fixed seeded sample of its flattened elements instead (the same indices on every
+    run with the same arguments), sized in proportion to the array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items() if v.numel()}
+    total = sum(4 * v.numel() for v in arrays.values())
+    for name, v in arrays.items():
+        if total > budget:
+            keep = max(1, v.numel() * budget // total)
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), v.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -560,7 +579,11 @@ def main():
     ap.add_argument("--no-full", action="store_true", help="skip the complete 1000-step trajectory (full_trajectory)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of the hipGraph-captured step")
     ap.add_argument("--exchange-probe-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call returned as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.exchange_probe_child:
         return exchange_probe_child(args)
@@ -605,9 +628,12 @@ def main():
     torch.manual_seed(23 + rank)
     x = torch.randn(B, 3, S, S, device=dev)
 
+    last_call = []          # (sample, snapshot dict) of the latest call: what --dump-outputs writes
+
     def run_steps(x, idx):
-        img, _ = diff.sampler.sample((B, 3, S, S), sampling_kwargs=skw, denoise_sample_fn=diff.denoise_sample_fn,
-                                     denoise_sample_fn_kwargs=dkw, x_T=x, step_indices=idx)
+        img, inter = diff.sampler.sample((B, 3, S, S), sampling_kwargs=skw, denoise_sample_fn=diff.denoise_sample_fn,
+                                         denoise_sample_fn_kwargs=dkw, x_T=x, step_indices=idx)
+        last_call[:] = [img, inter]
         return img
 
     def barrier():
@@ -634,6 +660,9 @@ def main():
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * B / (1000.0 * (elapsed / args.steps))
     assert torch.isfinite(x).all()
+    if args.dump_outputs and rank == 0:
+        img, inter = last_call
+        dump_outputs(args.dump_outputs, dict(sample=img, pred_x0=inter["pred_x0"], x_inter=inter["x_inter"]))
 
     # ---- the metric in full: ONE complete 1000-step trajectory through the reference's entry
     # point -- LatentDiffusion.p_sample_loop('native') (ddpm.py:108-122 -> ddpm_sampler.py:194-238): 1000 captured steps,

@@ -335,6 +335,28 @@ def test_committed_bench_line_has_the_contract_fields(fname):
     assert c["kind"] in ("reference", "port")
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per non-empty array at full shape; past the byte budget a seeded sample of each
+    array, the same elements on every call, within the budget in all"""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = dict(sample=torch.randn(4, 3, 8, 8, generator=g), pred_x0=torch.randn(2, 4, 3, 8, 8, generator=g).double(),
+                  x_inter=torch.zeros(0, 4, 3, 8, 8))
+    bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert sorted(os.listdir(tmp_path / "full")) == ["pred_x0.npy", "sample.npy"]
+    for name in ("sample", "pred_x0"):
+        got = np.load(tmp_path / "full" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, arrays[name].float().numpy())
+    budget = 4 * 300
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= budget
+    for name in ("sample", "pred_x0"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < arrays[name].numel() and np.array_equal(a, b)
+        assert np.isin(a, arrays[name].float().numpy().ravel()).all()
+
+
 def test_library_exports_nothing_undeclared():
     """every `sgd_*` function the shared library exports is declared in include/sgdm_hip.h (no hidden entry points)"""
     import subprocess

@@ -146,8 +146,17 @@ def test_ddim_tables_bit_exact():
 def test_timestep_embedding_and_snapshots():
     v = load_npz("diffusion.npz")
     t = torch.from_numpy(v["temb.t"])
+    eps = float(np.finfo(np.float32).eps)
     for dim in (32, 64, 128):
-        assert np.array_equal(U.timestep_embedding(t, dim).numpy(), v[f"temb.{dim}"])
+        got, ref = U.timestep_embedding(t, dim).numpy(), v[f"temb.{dim}"]
+        # fp32 exp / cos / sin may round their last bit differently on another host's vector code path; one ulp of a
+        # frequency moves its argument t * freq by ulp(t * freq) before the cosine, so each element is held to its own
+        # conditioning: a few ulp of (1 + |t * freq|)
+        half = dim // 2
+        arg = np.abs(v["temb.t"][:, None].astype(np.float64) * np.exp(-np.log(10000.0) * np.arange(half) / half)[None])
+        assert got.shape == ref.shape and got.dtype == ref.dtype
+        assert (np.abs(got.astype(np.float64) - ref) <= 4 * eps * (1 + np.concatenate([arg, arg], 1))).all(), dim
+        assert np.array_equal(got[v["temb.t"] == 0], ref[v["temb.t"] == 0])     # t = 0: cos 0 = 1, sin 0 = 0 exactly
     for total in (10, 50, 250, 1000):
         assert D.snapshot_indices(total) == v[f"snap.{total}"].tolist()
 
@@ -275,10 +284,16 @@ def test_train_step_loss_and_grads(name):
         if p.grad is not None:
             sq += float((p.grad.double() ** 2).sum())
     assert abs(sq - float(v[tag + ".grad_sqnorm"])) < 1e-4 * float(v[tag + ".grad_sqnorm"])
-    for key in v:
-        if key.startswith(tag + ".grad."):
-            pname = key[len(tag + ".grad."):]
-            assert max_rel(sd[pname].grad, v[key]) < 5e-5, pname
+    grads = {key[len(tag + ".grad."):]: v[key] for key in v if key.startswith(tag + ".grad.")}
+    scale = max(float(np.abs(g).max()) for g in grads.values())
+    for pname, ref in grads.items():
+        if float(np.abs(ref).max()) < 1e-6 * scale:
+            # analytically zero (output_blocks.8.0.out_layers.3.bias: a per-channel shift straight into the final GroupNorm,
+            # one channel per group at ch = 32): both sides are rounding residue whose digits depend on the host's vector
+            # code paths, so it is held to being residue, not matched digit for digit
+            assert float(sd[pname].grad.abs().max()) < 1e-6 * scale, pname
+        else:
+            assert max_rel(sd[pname].grad, ref) < 5e-5, pname
     assert sorted(v[tag + ".loss_keys"].tolist()) == ["train/ddpm_loss", "train/epoch_stats_x",
                                                       "train/epoch_stats_y", "train/loss"]
 
