@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: classifier-free-guided 1000-step DDPM sampling of 64x64 images.
 
-    python bench.py --gpus N --steps K --warmup W [--prec f32|f16x3|bf16x3] [--workload c2|c5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--prec f32|f16x3|bf16x3] [--workload c2|c5] [--dump-outputs DIR] [--full]
 
 A "step" is one CFG sampling step of the reference's native sampler on one batch of synthetic input:
 one UNet evaluation at 2B (cond + uncond) + the fused x0/posterior update (ddpm_sampler.py:154-192).
@@ -11,14 +11,16 @@ Sampling shards by images with no collective: N ranks sample N independent batch
 
 metric value = images/s of a full 1000-step trajectory = (N * B) / (1000 * t_step).
 
-One JSON line on rank 0 with `roofline` (dominant kernel: the fused implicit-GEMM conv, timed with HIP
-events around every launch in an instrumented pass) and `cpu_baseline` (the CPU oracle -- the
-restatement of the reference's UNet -- timed on this box's host cores on a bounded sample), plus sub-records of
-the same run: `train_step` (metric's second half; `train_step_bs40`: configs[2]'s per-GPU batch; `exchange_world1`: the
-data-parallel step through a one-rank RCCL group), `f32_exact` (the headline workload in exact-fp32 MFMA arithmetic), `c5` /
-`c4` (BASELINE.json configs[4] / [3], unetca_fast bs=80: sampling step + train step) and `c1` (configs[0] at its true shape
-on the GPU, eager launches vs the hipGraph-captured step).  `roofline` also carries the device's own ceiling measured in the
-run (`device_mfma_tflops`, `frac_of_device_ceiling`, `device_copy_tbps`).
+A plain run does only what that figure needs: set-up, W warm-up steps, K timed steps, the --dump-outputs arrays and one JSON
+line on rank 0.  Everything else is measured with --full, in the same line: `full_trajectory` (one complete 1000-step
+trajectory), `roofline` (dominant kernel: the fused implicit-GEMM conv, timed with HIP events around every launch in an
+instrumented pass) and `cpu_baseline` (the CPU oracle -- the restatement of the reference's UNet -- timed on this box's host
+cores on a bounded sample), plus sub-records of the same run: `train_step` (metric's second half; `train_step_bs40`:
+configs[2]'s per-GPU batch; `exchange_world1`: the data-parallel step through a one-rank RCCL group), `f32_exact` (the headline
+workload in exact-fp32 MFMA arithmetic), `c5` / `c4` (BASELINE.json configs[4] / [3], unetca_fast bs=80: sampling step + train
+step) and `c1` (configs[0] at its true shape on the GPU, eager launches vs the hipGraph-captured step).  `roofline` also carries
+the device's own ceiling measured in the run (`device_mfma_tflops`, `frac_of_device_ceiling`, `device_copy_tbps`).  The
+--no-* options leave single legs out of a --full run; in a plain run those records are null.
 
 Multi-GPU: the driver launches one rank per GPU through torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment).  Run by hand as `python bench.py --gpus N` it launches the N ranks ITSELF -- as child processes, before
@@ -568,6 +570,9 @@ def main():
     ap.add_argument("--prec", default=os.environ.get("SGDM_PREC", "f16x3"))
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every leg beside the headline figure (the 1000-step trajectory, "
+                         "roofline and device probe, train steps, the other workloads and precisions, the CPU baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-train", action="store_true")
@@ -576,7 +581,7 @@ def main():
     ap.add_argument("--no-exchange-probe", action="store_true",
                     help="skip the one-rank RCCL run of the data-parallel step (train_step.exchange_world1)")
     ap.add_argument("--no-extra", action="store_true", help="skip the f32_exact / c5 / c1 sub-records")
-    ap.add_argument("--no-full", action="store_true", help="skip the complete 1000-step trajectory (full_trajectory)")
+    ap.add_argument("--no-trajectory", action="store_true", help="skip the complete 1000-step trajectory (full_trajectory)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of the hipGraph-captured step")
     ap.add_argument("--exchange-probe-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -587,6 +592,9 @@ def main():
 
     if args.exchange_probe_child:
         return exchange_probe_child(args)
+    if not args.full:
+        # a plain run: the headline figure alone, every leg beside it is left out
+        args.no_trajectory = args.no_profile = args.no_train = args.no_extra = args.no_cpu_baseline = True
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -669,7 +677,7 @@ def main():
     # the 9 pred_x0 / x_inter snapshots and the uint8 tail -- wall clock, max over ranks.  `value` above stays the K timed
     # steps the bench contract prescribes; this is the steady-state figure beside it (~18 s per GPU).
     full = None
-    if not args.no_full:
+    if not args.no_trajectory:
         with torch.no_grad():
             barrier()
             t0 = time.perf_counter()

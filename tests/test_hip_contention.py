@@ -12,7 +12,8 @@ start only when others exit.  Single-GPU stand-in for that: `sgd_debug_occupy` p
   * the balanced tail's bounded poll: stale arrival counters poison the output with NaN and set the health word of the
     workspace instead of hanging the device;
   * `bench.py --gpus 2` as a fresh child process (two ranks over gloo sharing the one GPU): the multi-GPU leg's rank
-    plumbing, gradient exchange, initial-state broadcast and cross-rank checksum run end to end.
+    plumbing, gradient exchange, initial-state broadcast and cross-rank checksum run end to end;
+  * a plain `bench.py` run as a fresh child process: the headline figure alone, the last timed step's outputs dumped.
 """
 import ctypes as C
 import json
@@ -347,8 +348,8 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     env = dict(os.environ, SGDM_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extra",
-           "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-extra", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -367,3 +368,29 @@ def test_bench_two_ranks_gloo_on_one_gpu():
     assert len(tr["exchange_buckets"]) >= 3
     assert line["train_step_bs40"]["batch_per_gpu"] == 40 and line["train_step_bs40"]["global_batch"] == 80
     assert line["roofline"]["frac"] > 0 and line["cpu_baseline"] is None
+
+
+def test_bench_plain_run_prints_the_headline_alone(tmp_path):
+    """`python bench.py` without --full as a fresh child process: one line with the headline figure and nothing measured
+    beside it (those legs are --full's), and under --dump-outputs the sample the last timed step returned"""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "cfg_sampled_images_per_sec_64x64_1000step_ddpm" and line["unit"] == "images/s"
+    assert line["higher_is_better"] is True and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["config"]["batch_per_gpu"] == 40 and line["dtype"].startswith("f32 as 3xf16")
+    # images/s of a 1000-step trajectory = B / (1000 * s per step) = B / ms per step
+    assert line["value"] > 0 and abs(line["value"] - 40 / line["ms_per_step"]) < 1e-3 * line["value"]
+    for k in ("roofline", "cpu_baseline", "train_step", "train_step_bs40", "full_trajectory"):
+        assert line[k] is None, k
+    assert not {"c1", "c4", "c5", "c2_bs80", "f32_exact"} & set(line)
+    import numpy as np
+    sample = np.load(tmp_path / "sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (40, 3, 64, 64) and np.isfinite(sample).all()

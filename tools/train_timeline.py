@@ -4,8 +4,8 @@ with start / end timestamps), cuts it into training steps at the fused optimizer
 and reports, for the steady-state steps: span, device-busy time (union of the kernel intervals), idle time, the number of
 kernels, the idle time attributed to the kernel that FOLLOWS each gap (grouped by kernel name), and the largest gaps.
 
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o t -- python3 $REPO/bench.py --no-extra \\
-        --no-cpu-baseline --no-full --no-profile --no-train40 --no-exchange-probe --steps 2 --warmup 1
+    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d /tmp/tl -o t -- python3 $REPO/bench.py --full --no-extra \\
+        --no-cpu-baseline --no-trajectory --no-profile --no-train40 --no-exchange-probe --steps 2 --warmup 1
     python tools/train_timeline.py /tmp/tl/**/t_kernel_trace.csv [--marker adamw_ema_kernel]
 """
 import argparse
