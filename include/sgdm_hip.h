@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SGD_ABI_VERSION 21
+#define SGD_ABI_VERSION 22
 int sgd_abi_version(void);
 /* 16 hex digits identifying the sources and flags the library was compiled from (build.py: source_id()); static storage.
  * __graft_entry__.build() and tests/test_boundary_cpu.py compare it with the tree on disk. */
@@ -336,6 +336,29 @@ int sgd_ddpm_step_dev(const float* x, const float* eps_nhwc, const float* z, int
 int sgd_ddim_step_dev(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
                       const float* coef_dev, float temperature, int32_t clip, int32_t b, int32_t c, int32_t hw,
                       float* x_out, float* x0_out, void* stream);
+/* PNDM update (pndm_sampler.py:96-141, F-PNDM: four Runge-Kutta sub-steps x 3, then 4th-order linear multistep): ONE
+ * launch per UNet evaluation.  Everything that changes between evaluations is read from DEVICE memory -- the row below,
+ * the accumulator `acc`, the warm-up start image `base` and the history `ring` [3][b*c*hw] -- so one captured step
+ * replays for every evaluation of a trajectory (sgdm_amd/diffusion.py: PNDM_Sampler).  Per element, with e the guided eps:
+ *   RK0  : ring[slot1] = e, acc = (1/6) e,  base = x,  x_out = transfer(x, e)
+ *   RK12 : acc = acc + (1/3) e,                        x_out = transfer(base, e)
+ *   RK3  :                                             x_out = transfer(base, acc + (1/6) e)
+ *   PLMS : r = (1/24)(55 e - 59 ring[slot1] + 37 ring[slot2] - 9 ring[slot3]),  ring[slot3] = e,  x_out = transfer(x, r)
+ *   transfer(s, r) = s + d * (c1 * s - c2 * r)   (Eq. 9, pndm_sampler.py:128-141; each product rounded, as torch does)
+ * d = at_next - at, c1 = 1 / (sqrt(at) (sqrt(at) + sqrt(at_next))),
+ * c2 = 1 / (sqrt(at) (sqrt((1 - at_next) at) + sqrt((1 - at) at_next))), formed by the caller in fp32.
+ * eps_nhwc as for the step kernels above (cfg_mode 0: b*c one-channel planes).  x_out == x allowed; acc, base and ring must
+ * not alias x, x_out or each other.  Ring slots are taken mod 3. */
+#define SGD_PNDM_RK0 0
+#define SGD_PNDM_RK12 1
+#define SGD_PNDM_RK3 2
+#define SGD_PNDM_PLMS 3
+typedef struct sgd_pndm_row {
+    float d, c1, c2, reserved;
+    int32_t phase, slot1, slot2, slot3;
+} sgd_pndm_row;
+int sgd_pndm_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, float w, const sgd_pndm_row* row_dev,
+                  float* acc, float* base, float* ring, int32_t b, int32_t c, int32_t hw, float* x_out, void* stream);
 /* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s

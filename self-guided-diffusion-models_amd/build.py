@@ -28,6 +28,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # per-file extras.  igemm: no SLP vectorisation -- packed f32 VALU (v_pk_fma_f32 ...) next to a saturated matrix pipe costs
 # more issue time than the two scalar ops it replaces (measured +2..3 % on the conv launches with it off)
 FILE_FLAGS = {"igemm.hip": ["-fno-slp-vectorize"], "pack.hip": ["-fno-slp-vectorize"]}      # (pack.hip: part of igemm.hip up to round 5)
+# pndm.hip: no contraction -- the PNDM update is the reference's torch op sequence, rounding for rounding (a later
+# -ffp-contract=off overrides the global =fast; `#pragma clang fp contract(off)` does not)
+FILE_FLAGS["pndm.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

@@ -20,7 +20,7 @@ RS_NONE, RS_AVGPOOL2, RS_UP2, RS_ZEROUP2 = 0, 1, 2, 3
 PRO_NONE, PRO_AFFINE_NC, PRO_LN_ROW = 0, 1, 2
 PREC_F32, PREC_F16X3, PREC_BF16X3 = 0, 1, 2
 PREC_BY_NAME = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3}
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 # sgd_igemm_args.tune (include/sgdm_hip.h: SGD_TUNE_*): per-call schedule overrides for parity tests and A/B tools
 TUNE_BN128, TUNE_BN256, TUNE_FLAT2, TUNE_DEFER, TUNE_PLAIN_SCHEDULE, TUNE_LN_PACKED, TUNE_NO_SMALL = 1, 2, 4, 8, 16, 32, 64
@@ -134,6 +134,7 @@ SIGNATURES = {
     "sgd_geglu": (i32, [vp, i64, i32, vp, vp]),
     "sgd_to_uint8": (i32, [vp, i64, vp, vp]),
     "sgd_cfg_combine": (i32, [vp, i32, f32, i32, i32, i32, vp, vp]),
+    "sgd_pndm_step": (i32, [vp, vp, i32, f32, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

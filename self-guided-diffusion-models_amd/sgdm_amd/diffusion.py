@@ -3,7 +3,8 @@
 Mirrors (reference, /root/reference):
     diffusion/ddpm.py:24-126                      LatentDiffusion
     diffusion/sampler/ddpm_sampler.py:16-238      Schedule_DDPM   ('native' 1000-step ancestral sampler)
-    diffusion/sampler/ddim_plms_sampler.py:25-391 DDIMSampler     ('ddim')
+    diffusion/sampler/ddim_plms_sampler.py:25-391 DDIMSampler     ('ddim', 'plms')
+    diffusion/sampler/pndm_sampler.py:13-211      PNDM_Sampler    ('pndm', include/sgdm_hip.h: sgd_pndm_step)
     dynamic/diffusionmodules/util.py:23-74        schedules / DDIM tables (deterministic host math)
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
@@ -14,6 +15,7 @@ per-step mask uniform_ and z) are kept in the reference's order so seeded runs l
 import copy
 import ctypes as C
 import os
+import warnings
 from functools import partial
 
 import numpy as np
@@ -188,14 +190,19 @@ class _GraphedStep:
             with torch.cuda.graph(self.graph, stream=side):
                 st = torch.cuda.current_stream(dev).cuda_stream
                 eng.launch(st)
-                if kind == "ddpm":
-                    L.check(self.lib.sgd_ddpm_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
-                                                       clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st), "sgd_ddpm_step_dev")
-                else:
-                    L.check(self.lib.sgd_ddim_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
-                                                       float(temperature), clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st),
-                            "sgd_ddim_step_dev")
+                self._launch_update(st, img, mode, w, B, Cc, hw, kind, clip, temperature)
         torch.cuda.current_stream(dev).wait_stream(side)
+
+    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
+        """the update kernel of the captured step (reads the UNet's eps from the engine, updates img in place)"""
+        eng = self.eng
+        if kind == "ddpm":
+            L.check(self.lib.sgd_ddpm_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
+                                               clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st), "sgd_ddpm_step_dev")
+        else:
+            L.check(self.lib.sgd_ddim_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
+                                               float(temperature), clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st),
+                    "sgd_ddim_step_dev")
 
     def begin(self, img, cond, layout):
         """start of a trajectory: x_T and the guidance tensors into the static buffers; packed weights re-checked"""
@@ -217,6 +224,33 @@ class _GraphedStep:
         else:
             self.z.copy_(noise)
         self.coef.copy_(coef_row)
+        self.graph.replay()
+
+
+class _GraphedPNDMStep(_GraphedStep):
+    """The captured step of the PNDM sampler: UNet at 2B + ``sgd_pndm_step``.  Its static buffers are the Runge-Kutta
+    accumulator, the warm-up start image and the 3-slot eps history; ``row`` (include/sgdm_hip.h: sgd_pndm_row) says which
+    update the replay performs, so ONE graph serves warm-up and multistep evaluations alike.  No ``z`` is drawn: the only
+    RNG use per evaluation is the cond-drop mask's ``uniform_``, as in the reference (pndm_sampler.py:176-208)."""
+
+    def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
+        self.acc = torch.empty_like(img)
+        self.base = torch.empty_like(img)
+        self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
+        self.row = torch.zeros(8, dtype=torch.int32, device=img.device)
+        super().__init__(runner, eng, img, kind, clip, temperature)
+
+    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
+        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.row), _ptr(self.acc),
+                                       _ptr(self.base), _ptr(self.ring), B, Cc, hw, _ptr(img), st), "sgd_pndm_step")
+
+    def step(self, t_row, row):
+        """t_row: [B] long device tensor; row: [8] int32 device tensor (one sgd_pndm_row)"""
+        if self.has_mask:
+            self.u.uniform_(0, 1)                       # prob_mask_like: the eager path's only draw per evaluation
+            torch.lt(self.u, self.p, out=self.mask)
+        self.t.copy_(t_row)
+        self.row.copy_(row)
         self.graph.replay()
 
 
@@ -635,6 +669,111 @@ class DDIMSampler(object):
         return img, dict(x_inter=torch.cat(inter, 0), pred_x0=torch.cat(pred, 0))
 
 
+PNDM_RK0, PNDM_RK12, PNDM_RK3, PNDM_PLMS = 0, 1, 2, 3            # include/sgdm_hip.h: SGD_PNDM_*
+
+
+class PNDM_Sampler(object):
+    """pndm_sampler.py:147-211 with its PNDMScheduler (:13-145): F-PNDM, 12 Runge-Kutta warm-up evaluations then one
+    4th-order linear multistep evaluation per time.  Per evaluation ONE UNet call (at 2B on the fused-CFG path) and ONE
+    ``sgd_pndm_step`` launch; the per-evaluation scalars form a table uploaded once per trajectory (``plan``).
+
+    Kept from the reference: its own schedule (fp32 linear betas whatever the model's ``beta_schedule``, a trailing 0.0 so
+    that every lookup reads ``alphas_cumprod[t + 1]``); no clipping and no noise after ``x_T`` (``clip_denoised``, ``dtp``,
+    ``temperature``, ``noise_dropout`` and ``vis`` are ignored); the last multistep evaluation (t = t_next = 0) is a no-op
+    update but is still evaluated; the return value ``(image, dict(pred_x0=image))``.  Tests may inject ``x_T=``.
+    Step counts whose inference times include 999 (n = 3, 9, 27, 36-37, 101-111, 251-333, 501-1000) start the warm-up at the
+    appended alphas_cumprod[1000] = 0.0: the reference's transfer divides by zero there, and the same infinite scalars go
+    into the table here unchanged."""
+
+    def __init__(self, ddpm_num_timesteps, beta_start, beta_end, beta_schedule="linear", tensor_format="pt", device="cuda"):
+        self.ddpm_num_timesteps = ddpm_num_timesteps
+        self.device = device
+        self.beta_start, self.beta_end = beta_start, beta_end
+        self.beta_schedule = beta_schedule          # stored only: the reference's scheduler is always built linear
+        self.tensor_format = tensor_format
+        # pndm_sampler.py:31-45 (PNDMScheduler(timesteps, beta_start, beta_end) with its default beta_schedule)
+        betas = np.linspace(beta_start, beta_end, ddpm_num_timesteps, dtype=np.float32)
+        alphas_cumprod = np.cumprod(1.0 - betas, axis=0)
+        self.alphas_cumprod = torch.from_numpy(np.array(list(alphas_cumprod) + [0.0], dtype=np.float32))
+
+    def time_steps(self, num_inference_steps):
+        """(warm-up times, multistep times) of pndm_sampler.py:74-94.  ValueError where the reference fails with one:
+        fewer than four inference times (numpy broadcast) or num_inference_steps > ddpm_num_timesteps (range step 0)."""
+        T, n = self.ddpm_num_timesteps, int(num_inference_steps)
+        step = T // n
+        if step == 0:
+            raise ValueError(f"PNDM: num_timesteps={n} > {T} gives a time step of 0")
+        times = list(range(0, T, step))
+        if len(times) < 4:
+            raise ValueError(f"PNDM: num_timesteps={n} gives {len(times)} inference times; the warm-up needs 4")
+        last = np.array(times[-4:]).repeat(2) + np.tile(np.array([0, step // 2]), 4)
+        warmup = [int(v) for v in reversed(last[:-1].repeat(2)[1:-1])]
+        return warmup, list(reversed(times[:-3]))
+
+    def plan(self, num_inference_steps):
+        """(UNet time per evaluation, [E, 8] int32 table of sgd_pndm_row).  The transfer scalars are the reference's fp32
+        expressions (pndm_sampler.py:128-141) in IEEE fp32 arithmetic -- numpy float32, whose sqrt and divide are correctly
+        rounded on every host.  (torch's CPU sqrt is not: it differs from the correctly rounded value for ~14 % of fp32
+        inputs, by an amount that depends on the host CPU, so a table built with it would not be the same table on every
+        machine.  The reference on the GPU, its configured device, rounds sqrt and divide correctly, as here.)"""
+        warmup, plms = self.time_steps(num_inference_steps)
+        ev = []                                     # (t, t_prev, t_next, phase, slot1, slot2, slot3)
+        for j, t in enumerate(warmup):              # step_prk (:96-115)
+            ev.append((t, warmup[j // 4 * 4], warmup[min(j + 1, len(warmup) - 1)], (PNDM_RK0, PNDM_RK12, PNDM_RK12, PNDM_RK3)[j % 4],
+                       j // 4, 0, 0))
+        for k, t in enumerate(plms):                # step_plms (:117-126): ets[-2], ets[-3], ets[-4] in ring slots
+            ev.append((t, t, plms[min(k + 1, len(plms) - 1)], PNDM_PLMS, (k + 2) % 3, (k + 1) % 3, k % 3))
+        ac = self.alphas_cumprod.numpy()
+        at = ac[[e[1] + 1 for e in ev]]
+        at_next = ac[[e[2] + 1 for e in ev]]
+        one = np.float32(1)
+        with np.errstate(divide="ignore", invalid="ignore"):        # t = 999 reads the appended 0.0 (class docstring)
+            d = at_next - at
+            c1 = one / (np.sqrt(at) * (np.sqrt(at) + np.sqrt(at_next)))
+            c2 = one / (np.sqrt(at) * (np.sqrt((one - at_next) * at) + np.sqrt((one - at) * at_next)))
+        tab = torch.zeros(len(ev), 8, dtype=torch.int32)
+        tab[:, 0:3] = torch.from_numpy(np.ascontiguousarray(np.stack([d, c1, c2], 1), dtype=np.float32)).view(torch.int32)
+        tab[:, 4:8] = torch.tensor([e[3:] for e in ev], dtype=torch.int32)
+        return [e[0] for e in ev], tab
+
+    @torch.no_grad()
+    def sample(self, shape, sampling_kwargs, log_num_per_prog=100, denoise_sample_fn=None, denoise_sample_fn_kwargs=None,
+               **kwargs):
+        sk = sampling_kwargs
+        n = sk["num_timesteps"]
+        times, tab = self.plan(n)
+        if n > 250:
+            warnings.warn("according to the PNDM paper, most gains can be reaped when timestep<250, so it is not "
+                          "meaningful to set a timestep larger than 250")
+        dev = torch.device(self.device)
+        B, Cc = shape[0], shape[1]
+        hw = int(np.prod(shape[2:]))
+        x_T = kwargs.get("x_T")
+        # a private copy: the trajectory is updated in place below / in the captured step
+        img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32, copy=True).contiguous()
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        lib = runner.lib
+        tab_dev = tab.to(dev)
+        # PNDM ignores dtp and noise_dropout: only the model / guidance conditions of the captured step apply
+        if _graph_ok(runner, dict(sk, noise_dropout=0, dtp=1), kwargs):
+            g = _GraphedPNDMStep.get(runner, img, "pndm", 0)
+            ts_dev = torch.tensor(times, dtype=torch.long, device=dev).view(-1, 1).expand(len(times), B).contiguous()
+            for k in range(len(times)):
+                g.step(ts_dev[k], tab_dev[k])
+            img = g.img.clone()                     # the static buffer belongs to the cached graph
+            return img, dict(pred_x0=img)
+        acc, base = torch.empty_like(img), torch.empty_like(img)
+        ring = torch.empty((3,) + tuple(img.shape), device=dev)
+        for k, t in enumerate(times):
+            ts = torch.full((B,), t, device=dev, dtype=torch.long)
+            eps, mode, w, bb, cc = runner.eps(img, ts)
+            nxt = torch.empty_like(img)             # a new image per evaluation, as the reference's step returns
+            L.check(lib.sgd_pndm_step(_ptr(img), _ptr(eps), mode, w, _ptr(tab_dev[k]), _ptr(acc), _ptr(base), _ptr(ring),
+                                      bb, cc, hw, _ptr(nxt), _stream()), "sgd_pndm_step")
+            img = nxt
+        return img, dict(pred_x0=img)
+
+
 def to_uint8(x):
     """clip_unnormalize_to_zero_to_255 (diffusion_utils/util.py:99-100)"""
     if x.device.type != "cuda" or x.numel() == 0:
@@ -646,7 +785,8 @@ def to_uint8(x):
 
 
 class LatentDiffusion(nn.Module):
-    """diffusion/ddpm.py:24-126 (parameterization eps|x0, loss l1|l2|huber; samplers native + ddim)"""
+    """diffusion/ddpm.py:24-126 (parameterization eps|x0, loss l1|l2|huber; samplers native, ddim, plms and pndm --
+    the reference's 'tero' fails inside its own p_sample_loop)"""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -657,6 +797,8 @@ class LatentDiffusion(nn.Module):
             "native": self.sampler,
             "ddim": DDIMSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device, sampler_type="ddim"),
             "plms": DDIMSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device, sampler_type="plms"),
+            "pndm": PNDM_Sampler(ddpm_num_timesteps=h.num_timesteps, beta_start=h.linear_start, beta_end=h.linear_end,
+                                 beta_schedule=h.beta_schedule, device=h.device),
         }
 
     def set_denoise_fn(self, denoise_fn, denoise_sample_fn):
