@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SGD_ABI_VERSION 22
+#define SGD_ABI_VERSION 23
 int sgd_abi_version(void);
 /* 16 hex digits identifying the sources and flags the library was compiled from (build.py: source_id()); static storage.
  * __graft_entry__.build() and tests/test_boundary_cpu.py compare it with the tree on disk. */
@@ -42,7 +42,12 @@ const char* sgd_build_id(void);
  * -------------------------------------------------------------------------------------- */
 enum { SGD_MODE_FLAT = 0, SGD_MODE_CONV3 = 1 };
 enum { SGD_RS_NONE = 0, SGD_RS_AVGPOOL2 = 1, SGD_RS_UP2 = 2,
-       SGD_RS_ZEROUP2 = 3 /* x2 zero insertion: input of the adjoint of a stride-2 conv (Downsample backward) */ };
+       SGD_RS_ZEROUP2 = 3 /* x2 zero insertion: input of the adjoint of a stride-2 conv (Downsample backward) */,
+       /* nearest x2 upsample + 3x3 conv computed as four 2x2 sub-pixel convs at the INPUT resolution: output pixel
+        * (2i+a, 2j+b) = sum over r,s in {0,1} of V[a][b][r][s] . x[i+a-1+r, j+b-1+s] (zero outside the map), V the summed
+        * taps of sgd_pack_weight_subpixel_scaled.  Same result as SGD_RS_UP2 up to the rounding of V; split modes, 16-byte
+        * channel counts, no residual, no dropout -- sgd_igemm_subpixel_ok(args) says whether a launch qualifies */
+       SGD_RS_UP2_SUBPIXEL = 4 };
 enum { SGD_PRO_NONE = 0, SGD_PRO_AFFINE_NC = 1, SGD_PRO_LN_ROW = 2 };
 enum { SGD_PREC_F32 = 0, SGD_PREC_F16X3 = 1, SGD_PREC_BF16X3 = 2 };
 
@@ -134,7 +139,8 @@ enum {
     SGD_TUNE_WGRAD_NO_WS = 2048,          /* sgd_wgrad: the round-2 all-taps kernel instead of the wave-specialised one */
     SGD_TUNE_WGRAD_NO_PLANES = 4096,      /* sgd_wgrad: no pre-split operand planes even with scratch */
     SGD_TUNE_WGRAD_NO_PIPE = 8192,        /* sgd_wgrad, 1x1 / linear: synchronous staging (no register pipelining) */
-    SGD_TUNE_WGRAD_PLANES_ALWAYS = 16384  /* sgd_wgrad: pre-split planes also for a single 128-channel output tile */
+    SGD_TUNE_WGRAD_PLANES_ALWAYS = 16384, /* sgd_wgrad: pre-split planes also for a single 128-channel output tile */
+    SGD_TUNE_NO_SUBPIXEL = 32768          /* sgd_igemm_subpixel_ok: false (the caller keeps the direct SGD_RS_UP2 launch) */
 };
 int64_t sgd_igemm_work_bytes(void);
 /* Balanced-tail health word (DEVICE int32 inside the workspace, byte offset sgd_igemm_work_status_offset()): 0 after a
@@ -154,13 +160,35 @@ int sgd_igemm_tail_layout(int32_t total_tiles, int32_t nchunks, int32_t taps, in
  *   keep  <=>  (index & 1 ? h >> 16 : h & 0xFFFF) >= (uint32_t)(p * 65536) */
 
 int sgd_igemm(const sgd_igemm_args* args /* HOST pointer */, void* stream);
-/* number of per-image partial-statistics slots the epilogue of this launch writes (see args->stats) */
+/* number of per-image partial-statistics slots the epilogue of this launch writes (see args->stats); with
+ * resample = SGD_RS_UP2_SUBPIXEL the slots of the four output parities ([parity][input-resolution tile]) */
 int sgd_igemm_stats_parts(const sgd_igemm_args* args /* HOST pointer */);
+/* 1 if the launch `args` describes -- a nearest-upsample 3x3 conv, resample SGD_RS_UP2 or SGD_RS_UP2_SUBPIXEL -- may run
+ * as the sub-pixel conv (resample = SGD_RS_UP2_SUBPIXEL, weights of sgd_pack_weight_subpixel_scaled): a split mode,
+ * stride 1, 16-byte channel counts (c0, c1 % 4 == 0, whole 32-channel chunks per source), the 128-column tiles (cout a
+ * multiple of 128 and not the small-launch rule's 32-column tile), no residual, no dropout, and statistics only where
+ * the input-resolution tiles hold whole images (no two images per tile); never with SGD_TUNE_NO_SUBPIXEL.  0 otherwise:
+ * the caller keeps the direct SGD_RS_UP2 launch.  cin_p / cout_p / pointers are not read. */
+int sgd_igemm_subpixel_ok(const sgd_igemm_args* args /* HOST pointer */);
 
 /* bytes of the packed weight buffer for given dims; w_src is [cout, cin, k, k] (OIHW) or [cout, cin] */
 int64_t sgd_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ksize, int32_t prec);
 int sgd_pack_weight(const float* w_src, void* w_dst, int32_t cout, int32_t cin, int32_t ksize,
                     int32_t prec, int32_t* cin_p, int32_t* cout_p /* HOST out */, void* stream);
+
+/* Sub-pixel weights of a nearest-x2-upsample 3x3 conv (SGD_RS_UP2_SUBPIXEL), split modes only.  w_src is the OIHW
+ * [cout, cin, 3, 3] fp32 weight W[dy][dx] (dy, dx in -1..1).  For output parity (a, b) and tap (r, s) in {0,1}^2,
+ *   V[a][b][r][s] = sum over dy in R(a)[r], dx in R(b)[s] of W[dy][dx],  R(0) = ({-1}, {0, +1}), R(1) = ({-1, 0}, {+1}),
+ * summed in a fixed order: rows outer, columns inner, both ascending -- (W[y0][x0] + W[y0][x1]) + (W[y1][x0] + W[y1][x1])
+ * for four terms, W[y0][x] + W[y1][x] / W[y][x0] + W[y][x1] for two.  Layout: 4 parities (p = 2a + b), each in the
+ * sgd_pack_weight fragment order [cin_p/32][4 taps (t = 2r + s)][cout_p/32] of 4 KiB units.  The per-tensor scale is
+ * that of max|V| (sgd_weight_amax_subpixel), not max|W|. */
+int64_t sgd_packed_weight_subpixel_bytes(int32_t cout, int32_t cin, int32_t prec);
+/* folds max|V| over all 16 summed kernels of w_src [cout, cin, 3, 3] into *amax_bits (as sgd_weight_amax does for |w|) */
+int sgd_weight_amax_subpixel(const float* w_src, int32_t cout, int32_t cin, uint32_t* amax_bits, void* stream);
+int sgd_pack_weight_subpixel_scaled(const float* w_src, void* w_dst, int32_t cout, int32_t cin, int32_t prec,
+                                    const uint32_t* amax_bits, float* scale_inv_out, int32_t* cin_p, int32_t* cout_p /* HOST out */,
+                                    void* stream);
 
 /* sgd_pack_weight / sgd_pack_weight_dgrad with the per-tensor power-of-two scale described at sgd_igemm_args.w_scale_inv:
  * amax_bits is a DEVICE uint32 the caller zeroes; sgd_weight_amax (one or more calls: concatenated sources) folds
@@ -175,17 +203,19 @@ int sgd_pack_weight_scaled(const float* w_src, void* w_dst, int32_t cout, int32_
 /* Every weight of a model in three launches (the per-step re-pack of a training loop: one zero, one amax, one pack kernel
  * instead of two launches per tensor).  jobs / the block tables are DEVICE arrays the caller builds once:
  *   jobs[j]          one weight tensor: src (OIHW fp32), dst (packed buffer of sgd_packed_weight_bytes), dims of the FORWARD
- *                    weight, transpose (1: the dgrad operator), amax_bits / scale_inv as in sgd_pack_weight_scaled (NULL in
- *                    f32 mode), own_amax (0: amax_bits belongs to another job of the same tensor and is only read)
+ *                    weight, transpose (the job kind: 1 the dgrad operator, 2 the sub-pixel forward), amax_bits / scale_inv
+ *                    as in sgd_pack_weight_scaled (NULL in f32 mode), own_amax (0: amax_bits belongs to another job of the same tensor and is only read)
  *   *_block_job[b]   the job block b works on;  *_first[j] the first block of job j (n_jobs + 1 entries, ascending);
  *                    a job with own_amax == 0 has no amax blocks.  sgd_pack_job_blocks gives the block counts per job
  *                    (what the single-tensor entry points would launch) and the padded dims the packed operator has. */
+enum { SGD_PACK_FORWARD = 0, SGD_PACK_DGRAD = 1, SGD_PACK_SUBPIXEL = 2 /* 3x3 only: the layout of sgd_pack_weight_subpixel_scaled,
+                                                                          amax = max|V|, dst of sgd_packed_weight_subpixel_bytes */ };
 typedef struct sgd_pack_job {
     const float* src;
     void* dst;
     uint32_t* amax_bits;
     float* scale_inv;
-    int32_t cout, cin, ksize, transpose;
+    int32_t cout, cin, ksize, transpose;   /* transpose: the job kind, SGD_PACK_* */
     int32_t own_amax, reserved0;
 } sgd_pack_job;
 int sgd_pack_job_blocks(int32_t cout, int32_t cin, int32_t ksize, int32_t prec, int32_t transpose, int32_t* amax_blocks,

@@ -273,12 +273,23 @@ __device__ __forceinline__ float row16_sum(float v) {
 struct Tile {
     int n0c;                 // first output column
     int img0, ty0, tx0;      // CONV3 origin
+    int par;                 // sub-pixel: output parity 2a + b (0 otherwise)
     long m0;                 // FLAT origin
 };
 
+// SUB (sub-pixel instances): the M tiles are [parity][image group][tile] -- parity outermost, so the contiguous tile range of
+// an XCD (and the blocks it runs at the same time) shares ONE parity's weights instead of streaming four interleaved sets
+template <bool SUB>
 __device__ __forceinline__ Tile tile_at(const Geo& g, int lin, int bn, int tw, int th) {
     Tile t;
-    const int mtile = lin / g.nt, ntile = lin - mtile * g.nt;
+    int mtile = lin / g.nt;
+    const int ntile = lin - mtile * g.nt;
+    t.par = 0;
+    if constexpr (SUB) {
+        const int mq = g.mt >> 2;
+        t.par = mtile / mq;
+        mtile -= t.par * mq;
+    }
     t.n0c = ntile * bn;
     const int per_img = g.tiles_x * g.tiles_y;
     const int it = mtile / per_img, rem = mtile - it * per_img;
@@ -296,7 +307,10 @@ __device__ __forceinline__ Tile tile_at(const Geo& g, int lin, int bn, int tw, i
 template <int BN, int PREC, bool VEC, int TAPS, bool DEFER>
 struct IgemmBlock {
     // ------------------------------------------------------------------------------------------ compile-time shape
-    static constexpr bool CONV = TAPS == 9;
+    // TAPS = 4: the sub-pixel conv (SGD_RS_UP2_SUBPIXEL) -- a stride-1 3x3 halo at the input resolution, 2x2 taps placed by
+    // the tile's output parity, 16-byte inputs, split modes, 128-column (16x16x32 form) and 128 x 256 (32x32x16) tiles
+    static constexpr bool SUBPIX = TAPS == 4;
+    static constexpr bool CONV = TAPS == 9 || SUBPIX;
     // FLAT with TAPS = FG > 1 (round 4): a "chunk" is FG consecutive 32-channel planes of the 128 input rows, staged side
     // by side in one ring slot ([FG][128][LDA]) and consumed as FG K steps between two barriers -- the 1x1 / linear
     // launches then run in the conv kernel's rhythm (one s_barrier per chunk, loaders two chunks ahead in LDS) instead of
@@ -333,6 +347,7 @@ struct IgemmBlock {
 
     static constexpr int STG_LD = BN + 4;
     static_assert(!DEFER || (BN == 128 && TAPS == 9 && VEC && !M16), "loader-side epilogue: 3x3, 128-column tiles");
+    static_assert(!SUBPIX || (VEC && PREC != SGD_PREC_F32 && BN >= 128), "sub-pixel conv: 16-byte inputs, split modes, 128-column tiles");
 
     // ------------------------------------------------------------------------------------------ run-time state of the block
     const sgd_igemm_args& a;
@@ -423,7 +438,7 @@ struct IgemmBlock {
     // source-row table of tile k's A rows (index math once per tile, not per chunk)
     __device__ __forceinline__ void build_pixtab(int k, int t0, int nthr) const {
         if (k >= ntiles) return;
-        const Tile T = tile_at(g, lin_of(k), BN, TW, TH);
+        const Tile T = tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH);
         int2* tab = pixtab + (size_t)(k & 3) * g.pix;
         for (int pix = t0; pix < g.pix; pix += nthr) {
             int2 e;
@@ -520,7 +535,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
     const int dlt = tid - NCOMP;
     const int dcq = (dlt >> 6) * 8 + (dlt & 7), drg = (dlt & 63) >> 3;
     int dk = 0, dqs = 0, dnck = cend(0) - cbeg(0);
-    Tile dT = tile_at(g, lin_of(0), BN, TW, TH);       // tile dk - 1
+    Tile dT = tile_at<SUBPIX>(g, lin_of(0), BN, TW, TH);       // tile dk - 1
     int dcol = 0;                                      // first output channel of this thread's quad in tile dk - 1
     unsigned dsoff = 0xFFFFFFFFu;                      // statistics slot of tile dk - 1 (byte offset), this thread's quad
     f32x4 dres[8], ds1 = {0.f, 0.f, 0.f, 0.f}, ds2 = ds1;
@@ -590,7 +605,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
             if (req) { i0 = (16 * j) / nsl; i1 = (16 * (j + 1)) / nsl; }
             di0 = i0;
             if (dk > 0 && j == 0) {                    // per tile: its first channel / statistics slot for this thread
-                dT = tile_at(g, lin_of(dk - 1), BN, TW, TH);
+                dT = tile_at<SUBPIX>(g, lin_of(dk - 1), BN, TW, TH);
                 const Tile& T = dT;
                 dcol = T.n0c + dcq * 4;
                 const int part = (T.ty0 >> g.th_l2) * g.tiles_x + (T.tx0 >> g.tw_l2);
@@ -679,7 +694,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
                     if (++c.chunk == cend(c.k)) {
                         if (c.k + 1 < ntiles) {      // tile index math (integer divisions) once per tile, not per chunk
                             ++c.k; c.chunk = cbeg(c.k);
-                            c.img0 = tile_at(g, lin_of(c.k), BN, TW, TH).img0;
+                            c.img0 = tile_at<SUBPIX>(g, lin_of(c.k), BN, TW, TH).img0;
                         }
                         else c.chunk = cend(c.k) - 1;
                     }
@@ -750,7 +765,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
 #pragma unroll
                     for (int j = 0; j < AJ; ++j) issue_item(s2, j);
                 };
-                s2.k = 0; s2.chunk = cbeg(0); s2.img0 = tile_at(g, lin_of(0), BN, TW, TH).img0; fill(s2);
+                s2.k = 0; s2.chunk = cbeg(0); s2.img0 = tile_at<SUBPIX>(g, lin_of(0), BN, TW, TH).img0; fill(s2);
                 load_rows(0);
                 issue_coef(s2);
 #pragma unroll
@@ -814,7 +829,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
             float2 rst[NB_RING][AI];                                  // LayerNorm row statistics of the items
             struct Cur { int k, chunk; int m0; const float* ka; const float* kb; };
             auto open_tile = [&](Cur& c) {                           // per-tile scalars
-                const Tile T = tile_at(g, lin_of(c.k), BN, TW, TH);
+                const Tile T = tile_at<SUBPIX>(g, lin_of(c.k), BN, TW, TH);
                 c.m0 = (int)T.m0;
                 const long ko = tile_uni ? (long)(c.m0 / a.rows_per_n) * cin : 0;
                 // coefficient quads of a chunk: GroupNorm a / b of the tile's image, or LayerNorm gamma / beta;
@@ -952,7 +967,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
     auto tabref = [&](int k) {
         TabRef t;
         t.tab = pixtab + (size_t)(k & 3) * g.pix;
-        t.m0 = CONV ? 0 : tile_at(g, lin_of(k), BN, TW, TH).m0;
+        t.m0 = CONV ? 0 : tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH).m0;
         return t;
     };
     auto entry = [&](const TabRef& t, int pix) -> int2 {
@@ -1036,7 +1051,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
                 cx.tab = pixtab + (size_t)(k & 3) * g.pix;
                 cx.c = cx.chunk * KC + c4 * 4;
                 // per-image GroupNorm coefficients of this thread's channel quad (tile = one image)
-                cx.ko = (long)tile_at(g, lin_of(k), BN, TW, TH).img0 * cin + (cx.c < cin ? cx.c : 0);
+                cx.ko = (long)tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH).img0 * cin + (cx.c < cin ? cx.c : 0);
                 return cx;
             };
             Ctx cx = ctx_of(1);
@@ -1164,7 +1179,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::epilogue
             const int tx = row & (TW - 1), ty = (row >> g.tw_l2) & (TH - 1), nb = row >> (g.tw_l2 + g.th_l2);
             n = T.img0 + nb; oy = T.ty0 + ty; ox = T.tx0 + tx;
             okm[mt] = nb < g.nb && n < a.n;
-            orow = (n * a.ho + oy) * a.wo + ox;
+            if (SUBPIX) orow = (n * a.ho + 2 * oy + (T.par >> 1)) * a.wo + 2 * ox + (T.par & 1);   // input pixel -> its parity's output
+            else orow = (n * a.ho + oy) * a.wo + ox;
         } else {
             orow = (int)T.m0 + row;
             okm[mt] = orow < M;
@@ -1189,7 +1205,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::epilogue
             int n_img, part;
             if (CONV) {
                 n_img = T.img0;
-                part = ((T.ty0 >> g.th_l2) * g.tiles_x + (T.tx0 >> g.tw_l2)) * (BM / WM) + wm;
+                part = ((T.par * g.tiles_y + (T.ty0 >> g.th_l2)) * g.tiles_x + (T.tx0 >> g.tw_l2)) * (BM / WM) + wm;
             } else {
                 n_img = (int)(T.m0 / a.rows_per_n);
                 part = (int)((T.m0 % a.rows_per_n) / BM) * (BM / WM) + wm;
@@ -1351,7 +1367,20 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
         int l;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
         const int loff = M16 ? (l >> 5) * 2048 + (((l >> 4) & 1) * 32 + (l & 15)) * 16 : l * 16;
-        return reinterpret_cast<const char*>(a.w) + (size_t)(wn * NT + (tile_at(g, lin_of(k), BN, TW, TH).n0c >> 5)) * WUNIT + loff;
+        const Tile T = tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH);
+        // sub-pixel: the parity's own packed kernels, 4 taps x cin_p x cout_p x 4 bytes further per parity
+        const size_t pbase = SUBPIX ? (size_t)T.par * ((size_t)a.cin_p * a.cout_p * 16) : 0;
+        return reinterpret_cast<const char*>(a.w) + pbase + (size_t)(wn * NT + (T.n0c >> 5)) * WUNIT + loff;
+    };
+    // sub-pixel: LDS offset of the parity's first tap -- tap t = 2r + s of parity (a, b) reads halo (row + a + r, col + b + s)
+    auto par_off = [&](int k) __attribute__((always_inline)) {
+        if constexpr (SUBPIX) {
+            const int par = tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH).par;
+            return (par >> 1) * (g.hw * LDA) + (par & 1) * LDA;
+        } else {
+            (void)k;
+            return 0;
+        }
     };
 
     AccV acc[RB][CBN];
@@ -1382,7 +1411,10 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
     typename Frag16<PREC, 1>::B fb16[CBN];         // M16: weights of one 16-column block each
     const int rowstep = g.hw * LDA;                // LDS floats between halo rows
 
-    auto tap_off = [&](int tap) { return CONV ? (tap / 3) * rowstep + (tap % 3) * LDA : tap * (BM * LDA); };
+    auto tap_off = [&](int tap) {
+        if constexpr (SUBPIX) return (tap >> 1) * rowstep + (tap & 1) * LDA;          // + the parity offset in the chunk base
+        else return CONV ? (tap / 3) * rowstep + (tap % 3) * LDA : tap * (BM * LDA);
+    };
     // one K step: `acur` holds this step's chunk, `anext` the chunk the prefetches run into when `seam` (last tap)
     auto do_step = [&](const float* acur, const float* anext, auto tapc, auto parc, const char* wnext) {
         constexpr int tap = decltype(tapc)::value;
@@ -1446,10 +1478,11 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
         for (int ks = 0; ks < NKS; ++ks) fb[ks].load(wp, ks);
     }
     SYNC();                               // pairs with the loaders' prologue barrier: chunks 0 AND 1 are staged
+    int pcur = par_off(0);                         // sub-pixel: parity offset of the current tile (0 otherwise)
 #pragma unroll
     for (int st = 0; st < (M16 ? RB : DEPTH); ++st) {
-        if constexpr (M16) ring[st].load(As + aoff[st % RB], lane >> 4);
-        else ring[st].load(As + aoff[st % MT], st / MT, lh);
+        if constexpr (M16) ring[st].load(As + pcur + aoff[st % RB], lane >> 4);
+        else ring[st].load(As + pcur + aoff[st % MT], st / MT, lh);
     }
     int aslot = 0;                                 // ring position of the current chunk
     // CONV: ONE barrier per 32-channel chunk (9 K steps).  The weights never pass through LDS and the input tile of a
@@ -1458,6 +1491,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
     // chunk q+1 (slot complete since barrier q: the loaders run two chunks ahead, from the prologue on), while the
     // loaders fill slot (q+2) % 3 (last read in period q-1).
     for (int k = 0; k < ntiles; ++k) {
+        if (k > 0) pcur = par_off(k);
 #pragma unroll
         for (int i = 0; i < RB; ++i)
 #pragma unroll
@@ -1466,10 +1500,11 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
                 for (int r = 0; r < (M16 ? 4 : 16); ++r) acc[i][j][r] = 0.f;
         const char* const wseam = k + 1 < ntiles ? wstart_of(k + 1) : nullptr;   // first step of the next tile
         const int c_end = cend(k);
+        const int pnext = k + 1 < ntiles ? par_off(k + 1) : pcur;       // the next tile's first chunk may have another parity
         for (int chunk = cbeg(k); chunk < c_end; ++chunk) {
             const int naslot = aslot + 1 == NA ? 0 : aslot + 1;
-            const float* acur = As + (size_t)aslot * a_floats;
-            const float* anext = As + (size_t)naslot * a_floats;
+            const float* acur = As + (size_t)aslot * a_floats + pcur;
+            const float* anext = As + (size_t)naslot * a_floats + (chunk + 1 == c_end ? pnext : pcur);
             // step after this chunk's last one: next chunk, next tile, or (end of the stream) the same slice again
             const char* const wlast = chunk + 1 == c_end ? (wseam ? wseam : wp + (TAPS - 1) * wstep) : nullptr;
             // taps fully unrolled: tap offsets are compile-time, so no scalar index math sits between the MFMA blocks
@@ -1570,7 +1605,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
         // [32 channels x 32 pixels]: a lane owns ONE pixel (lane & 31) and its 16 registers are four runs
         // of 4 consecutive channels (8g + 4*(lane>>5) + 0..3).  => 16-byte residual loads / stores, and the
         // row index math runs twice per lane instead of 32 times.
-        const Tile T = tile_at(g, lin_of(k), BN, TW, TH);
+        const Tile T = tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH);
         // the lane index re-read from the hardware (all lanes are active here): what the epilogue derives from the lane is
         // computed per tile -- neither it nor `lane` itself has to survive the K loop in a register
         int lane_e;
@@ -1585,7 +1620,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
         auto run_epilogue = [&](auto partc) {
             constexpr bool PARTV = decltype(partc)::value;
             if (DBG(16) || ABL(8)) keep_acc();
-            else if (!a.res) epilogue<0, PARTV>(acc, T, wm, wn, lane_e, cb, wsk, part_base, nparts);
+            else if (SUBPIX || !a.res) epilogue<0, PARTV>(acc, T, wm, wn, lane_e, cb, wsk, part_base, nparts);   // (sub-pixel: no residual)
             else if (a.res_mode == SGD_RS_NONE) epilogue<1, PARTV>(acc, T, wm, wn, lane_e, cb, wsk, part_base, nparts);
             else if (NT > 1) __builtin_trap();      // resampled residuals: 128-column tiles only (sgd_igemm picks the tile)
             else if (a.res_mode == SGD_RS_AVGPOOL2) epilogue<2, PARTV>(acc, T, wm, wn, lane_e, cb, wsk, part_base, nparts);
@@ -1610,7 +1645,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
             // are NOT carried across the epilogue -- registers the epilogue needs -- but requested again here: one L2
             // round trip per tile (~1 % of a tile's K loop).
             if (k + 1 < ntiles) {
-                const float* a0 = As + (size_t)aslot * a_floats;
+                const float* a0 = As + (size_t)aslot * a_floats + pnext;
                 if constexpr (M16) {
                     // the WEIGHTS of the next tile's first step (requested by the last step, 16 registers) are carried: asked
                     // for again here they would sit behind the acknowledgement of the epilogue's 16 stores (vmcnt is in
@@ -1672,11 +1707,12 @@ int launch1(const KArgs& ka, size_t smem, hipStream_t st) {
 }
 
 // vec: 0 scalar inputs, 1 16-byte inputs, 2 16-byte inputs + the loader-side epilogue (DEFER: 3x3, 128-column tiles, split modes)
-// taps: 9 conv, 1 flat (one 32-channel plane per barrier), 2 flat with two planes per chunk (lean 16-byte launches)
+// taps: 9 conv, 4 sub-pixel conv, 1 flat (one 32-channel plane per barrier), 2 flat with two planes per chunk (lean 16-byte launches)
 template <int BN, int PREC>
 int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
     const bool conv = taps == 9;
 #ifdef SGDM_IGEMM_NOPK
+    if (taps == 4) return SGD_ERR_ARG;
     // the unit compiled without packed-f32 code generation (see the end of this file) serves the 1x1 / linear launches with
     // the LayerNorm-row prologue only: no 3x3 instance is instantiated here
     if (conv) return SGD_ERR_ARG;
@@ -1689,6 +1725,10 @@ int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
         return vec ? launch1<BN, PREC, true, 1>(ka, smem, st) : launch1<BN, PREC, false, 1>(ka, smem, st);
     }
 #else
+    if (taps == 4) {                              // sub-pixel conv: split modes, 16-byte inputs, 128 / 256-column tiles
+        if constexpr (PREC != SGD_PREC_F32 && BN >= 128) return launch1<BN, PREC, true, 4>(ka, smem, st);
+        return SGD_ERR_ARG;
+    }
     if constexpr (BN == 256) {                    // chosen for 16-byte launches only
         if (conv) return launch1<BN, PREC, true, 9>(ka, smem, st);
         return taps == 2 ? launch1<BN, PREC, true, 2>(ka, smem, st) : launch1<BN, PREC, true, 1>(ka, smem, st);

@@ -31,17 +31,23 @@ static int make_geo(const sgd_igemm_args& a, Geo& g, int bn, int& na, int fg = 1
     if (a.mode == SGD_MODE_CONV3) {
         if (a.n <= 0 || a.hi <= 0 || a.wi <= 0 || (a.stride != 1 && a.stride != 2)) return SGD_ERR_ARG;
         if (a.stride == 2 && a.resample != SGD_RS_NONE) return SGD_ERR_ARG;
+        if (a.resample < SGD_RS_NONE || a.resample > SGD_RS_UP2_SUBPIXEL) return SGD_ERR_ARG;
+        // sub-pixel (SGD_RS_UP2_SUBPIXEL): the conv runs on the input map itself -- a stride-1 3x3 halo at the input
+        // resolution, four times the M tiles (one set per output parity); ho x wo stays the 2x output
+        const bool sub = a.resample == SGD_RS_UP2_SUBPIXEL;
         const bool up = a.resample == SGD_RS_UP2 || a.resample == SGD_RS_ZEROUP2;
         g.hc = a.resample == SGD_RS_AVGPOOL2 ? a.hi / 2 : (up ? a.hi * 2 : a.hi);
         g.wc = a.resample == SGD_RS_AVGPOOL2 ? a.wi / 2 : (up ? a.wi * 2 : a.wi);
         if (a.resample == SGD_RS_AVGPOOL2 && ((a.hi | a.wi) & 1)) return SGD_ERR_ARG;
-        const int ho = a.stride == 2 ? (g.hc + 1) / 2 : g.hc, wo = a.stride == 2 ? (g.wc + 1) / 2 : g.wc;
+        const int ho = a.stride == 2 ? (g.hc + 1) / 2 : g.hc * (sub ? 2 : 1), wo = a.stride == 2 ? (g.wc + 1) / 2 : g.wc * (sub ? 2 : 1);
         if (a.ho != ho || a.wo != wo) return SGD_ERR_ARG;
         if (!is_pow2(a.ho) || !is_pow2(a.wo) || a.ho < 2 || a.wo < 2) return SGD_ERR_ARG;
         if (a.res && a.res_mode == SGD_RS_UP2 && ((a.ho | a.wo) & 1)) return SGD_ERR_ARG;
+        if (sub && (a.res || a.drop_p != 0.f)) return SGD_ERR_ARG;
         if ((long)a.n * a.hi * a.wi >= (1L << 31)) return SGD_ERR_ARG;      // source rows are 32-bit in the tile table
-        int tw = a.wo < 16 ? a.wo : 16;
-        int th = BM / tw; if (th > a.ho) th = a.ho;
+        const int gho = sub ? a.hi : a.ho, gwo = sub ? a.wi : a.wo;         // the tiled (conv-output) grid
+        int tw = gwo < 16 ? gwo : 16;
+        int th = BM / tw; if (th > gho) th = gho;
         while (th * tw > BM) th >>= 1;
         if (a.stride == 2) { if (tw > 8) tw = 8; if (th > 8) th = 8; }   // big input halos: smaller spatial tile
         int nb = BM / (th * tw);
@@ -52,9 +58,9 @@ static int make_geo(const sgd_igemm_args& a, Geo& g, int bn, int& na, int fg = 1
         while (nb > 1 && 3 * (size_t)nb * g.hh * g.hw * LDA * 4 + (size_t)nb * g.hh * g.hw * 32 > 150 * 1024)
             nb >>= 1;
         g.tw_l2 = ilog2(tw); g.th_l2 = ilog2(th); g.nb = nb;
-        g.tiles_x = a.wo / tw; g.tiles_y = a.ho / th;
+        g.tiles_x = gwo / tw; g.tiles_y = gho / th;
         g.pix = nb * g.hh * g.hw;
-        g.mt = ((a.n + nb - 1) / nb) * g.tiles_x * g.tiles_y;
+        g.mt = ((a.n + nb - 1) / nb) * g.tiles_x * g.tiles_y * (sub ? 4 : 1);   // sub-pixel: [parity][image group][tile]
         g.fast_a = g.pix <= FAST_PIX ? 1 : 0;
         na = 3;
     } else if (a.mode == SGD_MODE_FLAT) {
@@ -74,7 +80,8 @@ static int make_geo(const sgd_igemm_args& a, Geo& g, int bn, int& na, int fg = 1
     const int ppt = bn >= 128 ? 1 : 4;                        // M slices per tile = compute-wave rows
     if (((a.cout | a.y_ld) & 3) == 0 && a.orows_in == 0) {
         if (a.mode == SGD_MODE_CONV3) {
-            if (g.nb == 1 && (1 << (g.tw_l2 + g.th_l2)) == BM) g.sparts = g.tiles_x * g.tiles_y * ppt;
+            if (g.nb == 1 && (1 << (g.tw_l2 + g.th_l2)) == BM)
+                g.sparts = g.tiles_x * g.tiles_y * ppt * (a.resample == SGD_RS_UP2_SUBPIXEL ? 4 : 1);   // [parity][tile][slice]
         } else if (a.rows_per_n > 0 && a.rows_per_n % BM == 0 && a.m % a.rows_per_n == 0) {
             g.sparts = a.rows_per_n / BM * ppt;
         }
@@ -96,6 +103,11 @@ static bool want_bn256(const sgd_igemm_args& a) {
     // balanced tail can cut it along K and two images share a tile -- 8x8 maps of >= 512 input channels (+7..21 %) -- and loses
     // 10..37 % elsewhere (16 x 256 -> 256 @32^2: 0.075 vs 0.055 ms; 32 x 512 -> 512 @16^2: 0.114 vs 0.092), as does "one round of
     // bigger tiles instead of a second, partly empty one" (80 x 1024 -> 1024 @8^2: 0.321 vs 0.277; 40 x 512 -> 512 @16^2: 0.141 vs 0.135)
+    // sub-pixel convs (4 K steps per staged chunk instead of 9: the loaders' share per flop is 2.25x the direct conv's): the
+    // bigger tile stages each chunk once for twice the MFMAs.  Measured (tools/ab_conv.py, UNet batch 80, f16x3 / bf16x3):
+    // 512 -> 512 @16^2 in: 0.451 / 0.439 ms vs 0.456 / 0.444 on the 128-column tile, 256 -> 256 @32^2 in: 0.483 / 0.463 vs
+    // 0.515 / 0.516 (profiles/r7_ab_subpixel_tiles.txt).  Whole rounds of 256-column tiles only: smaller launches unmeasured
+    if (a.mode == SGD_MODE_CONV3 && a.resample == SGD_RS_UP2_SUBPIXEL) return t256 >= 256;
     if (a.mode == SGD_MODE_CONV3 && a.prec != SGD_PREC_F32) return t128 <= 256 && a.ho * a.wo <= 64 && a.c0 + a.c1 >= 512;
     // whole rounds of 256 persistent blocks: a 128 x 256 tile costs 2 / 1.07 of a 128 x 128 one (measured, tools/ab_conv.py:
     // +5..9 % where both shapes fill the chip evenly), so it wins unless the coarser tiles quantise worse
@@ -144,6 +156,29 @@ extern "C" int sgd_igemm_stats_parts(const sgd_igemm_args* args) {
     return g.sparts;
 }
 
+// Sub-pixel rule (include/sgdm_hip.h: sgd_igemm_subpixel_ok): the ONE place that decides whether a nearest-upsample 3x3 conv
+// may run as four 2x2 convs at the input resolution; Python asks it instead of repeating the bounds.
+static bool subpixel_ok(const sgd_igemm_args& a0) {
+    if (a0.mode != SGD_MODE_CONV3 || (a0.resample != SGD_RS_UP2 && a0.resample != SGD_RS_UP2_SUBPIXEL)) return false;
+    if (a0.prec == SGD_PREC_F32 || (a0.tune & SGD_TUNE_NO_SUBPIXEL)) return false;   // f32: the bit-exact direct FMA chain
+    if (a0.stride != 1 || a0.res || a0.drop_p != 0.f) return false;
+    // 16-byte channel counts, whole 32-channel chunks per source (the instance is built for VEC inputs only)
+    if ((a0.c0 & 3) || (a0.c1 & 3) || (a0.c1 > 0 && a0.c0 % KC != 0)) return false;
+    // 128-column tiles (the launcher's 32-column small-launch tile, and layers of cout % 128 != 0, keep the direct launch)
+    if (column_tile(a0) != 128) return false;
+    sgd_igemm_args a = a0;
+    a.resample = SGD_RS_UP2_SUBPIXEL;
+    Geo g;
+    int na;
+    if (make_geo(a, g, 128, na) != SGD_OK) return false;
+    if (a.stats && g.sparts == 0) return false;                                       // statistics with two images per tile
+    const size_t smem = (size_t)na * g.pix * LDA * sizeof(float) + (size_t)g.pix * 32
+                        + (a.cout <= BIAS_LDS_MAX ? (size_t)((a.cout + 127) / 128 * 128) * sizeof(float) : 0);
+    return smem <= 160 * 1024;
+}
+
+extern "C" int sgd_igemm_subpixel_ok(const sgd_igemm_args* args) { return args && subpixel_ok(*args) ? 1 : 0; }
+
 extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
     SGD_CLEAR_ERR();
     if (!args) return SGD_ERR_ARG;
@@ -161,9 +196,11 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
     const bool vec = (a.c0 % 4 == 0) && (a.c1 % 4 == 0);
     // 128 x 256 tile (64 columns per compute wave): launches whose output channels allow it.  The packed-weight layout does
     // not depend on the tile (units of 32 output channels), so this is a launch-time choice.
+    const bool conv = a.mode == SGD_MODE_CONV3;
+    const bool sub = conv && a.resample == SGD_RS_UP2_SUBPIXEL;
+    if (sub && !subpixel_ok(a)) return SGD_ERR_ARG;
     if (bn == 128 && a.cout_p % 256 == 0 && vec && (!a.res || a.res_mode == SGD_RS_NONE) && want_bn256(a)) bn = 256;
     int na;
-    const bool conv = a.mode == SGD_MODE_CONV3;
     // Two planes per chunk (igemm_kernel<.., TAPS = 2>): OPT-IN, args.tune & SGD_TUNE_FLAT2.  Flat launches the lean loaders serve
     // (16-byte rows, no / per-image GroupNorm prologue, no dropout, whole 32-channel planes per source) with an even
     // number of planes.  Measured (round 4, tools/ab_conv.py, UNet batch 80): bit-identical to the one-plane instance,
@@ -177,7 +214,7 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
     // it, moving the surrounding code does.  Round 6: with packed-f32 code generation off the same two-plane instance passes
     // 240 of 240 launches that fail 238 of 240 with it on (tools/ln_hazard.py, profiles/r6_ln_hazard.txt), so every
     // LayerNorm launch of a split mode runs on the no-packed-f32 unit (ln_nopk below); the two-plane instance stays opt-in.
-    int taps = conv ? 9 : 1;
+    int taps = conv ? (sub ? 4 : 9) : 1;
     // LayerNorm-row prologue in a split mode: the unit without packed-f32 instructions (SGD_TUNE_LN_PACKED: the regular unit --
     // tools/ln_hazard.py reproduces the round-4 fault with it); only there may the two-plane instance serve that prologue
     const bool ln_nopk = !conv && a.pro == SGD_PRO_LN_ROW && a.prec != SGD_PREC_F32 && !(a.tune & SGD_TUNE_LN_PACKED);
@@ -228,7 +265,7 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
         if (conv && vec && bn == 128 && a.prec != SGD_PREC_F32 && ((a.cout | a.y_ld) & 3) == 0
             && (!a.res || a.res_mode == SGD_RS_NONE) && a.resample != SGD_RS_AVGPOOL2 && a.cout_p <= BIAS_LDS_MAX && nchunks >= 3
             && rows_out * a.y_ld * 4 < (1L << 32) && (!a.stats || (long)a.n * g.sparts * 2 * a.cout * 4 < (1L << 32))
-            && smem_defer <= 160 * 1024 && (a.tune & SGD_TUNE_DEFER)) {
+            && smem_defer <= 160 * 1024 && !sub && (a.tune & SGD_TUNE_DEFER)) {
             variant = 2;
             smem_launch = smem_defer;
         }

@@ -16,16 +16,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGDM_LIB_PATH") or os.path.join(_HERE, "lib", "libsgdm_hip.so")   # override: A/B builds (tools)
 
 MODE_FLAT, MODE_CONV3 = 0, 1
-RS_NONE, RS_AVGPOOL2, RS_UP2, RS_ZEROUP2 = 0, 1, 2, 3
+RS_NONE, RS_AVGPOOL2, RS_UP2, RS_ZEROUP2, RS_UP2_SUBPIXEL = 0, 1, 2, 3, 4
 PRO_NONE, PRO_AFFINE_NC, PRO_LN_ROW = 0, 1, 2
 PREC_F32, PREC_F16X3, PREC_BF16X3 = 0, 1, 2
 PREC_BY_NAME = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3}
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 # sgd_igemm_args.tune (include/sgdm_hip.h: SGD_TUNE_*): per-call schedule overrides for parity tests and A/B tools
 TUNE_BN128, TUNE_BN256, TUNE_FLAT2, TUNE_DEFER, TUNE_PLAIN_SCHEDULE, TUNE_LN_PACKED, TUNE_NO_SMALL = 1, 2, 4, 8, 16, 32, 64
 TUNE_WGRAD_GENERIC_NARROW, TUNE_WGRAD_NO_POOLED_PLANES, TUNE_WGRAD_F32 = 256, 512, 1024
 TUNE_WGRAD_NO_WS, TUNE_WGRAD_NO_PLANES, TUNE_WGRAD_NO_PIPE, TUNE_WGRAD_PLANES_ALWAYS = 2048, 4096, 8192, 16384
+TUNE_NO_SUBPIXEL = 32768
+# sgd_pack_job.transpose: the job kind
+PACK_FORWARD, PACK_DGRAD, PACK_SUBPIXEL = 0, 1, 2
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -56,6 +59,7 @@ SIGNATURES = {
     "sgd_build_id": (C.c_char_p, []),
     "sgd_igemm": (i32, [C.POINTER(IgemmArgs), vp]),
     "sgd_igemm_stats_parts": (i32, [C.POINTER(IgemmArgs)]),
+    "sgd_igemm_subpixel_ok": (i32, [C.POINTER(IgemmArgs)]),
     "sgd_igemm_work_bytes": (i64, []),
     "sgd_igemm_work_status_offset": (i64, []),
     "sgd_igemm_tail_layout": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
@@ -64,6 +68,9 @@ SIGNATURES = {
     "sgd_pack_weight": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), vp]),
     "sgd_weight_amax": (i32, [vp, i64, vp, vp]),
     "sgd_pack_weight_scaled": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), vp]),
+    "sgd_packed_weight_subpixel_bytes": (i64, [i32, i32, i32]),
+    "sgd_weight_amax_subpixel": (i32, [vp, i32, i32, vp, vp]),
+    "sgd_pack_weight_subpixel_scaled": (i32, [vp, vp, i32, i32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), vp]),
     "sgd_pack_job_blocks": (i32, [i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "sgd_pack_weights_batched": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, i32, vp]),
     "sgd_linear_splitk": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp]),

@@ -171,11 +171,15 @@ class _Packed:
     """device buffer holding one conv/linear weight in the igemm layout, refreshed when the source
     parameter(s) change (optimizer step / load_state_dict bump ``_version``)."""
 
-    def __init__(self, srcs, ksize, prec, pad=None):
+    def __init__(self, srcs, ksize, prec, pad=None, subpixel=False):
         self.srcs = srcs                     # list of parameters concatenated along dim 0
         self.ksize = ksize
         self.prec = prec
         self.pad = pad                       # _Pad: the packed operator is the zero-padded re-layout of the parameter
+        # subpixel: the 16 summed 2x2 kernels of a nearest-x2-upsample 3x3 conv (include/sgdm_hip.h: SGD_RS_UP2_SUBPIXEL),
+        # split modes only; its scale is that of max |V|, so it never lends its amax to the adjoint pack (AMAX_OF)
+        self.subpixel = subpixel
+        assert not subpixel or (ksize == 3 and pad is None and prec != L.PREC_F32)
         self.cout = sum(s.shape[0] for s in srcs)
         self.cin = srcs[0].shape[1]
         if pad is not None:
@@ -183,7 +187,8 @@ class _Packed:
             self.cout = pad.n_rows if pad.rows is not None else self.cout
             self.cin = pad.n_cols if pad.cols is not None else self.cin
         lib = L.load()
-        nbytes = lib.sgd_packed_weight_bytes(self.cout, self.cin, ksize, prec)
+        nbytes = (lib.sgd_packed_weight_subpixel_bytes(self.cout, self.cin, prec) if subpixel
+                  else lib.sgd_packed_weight_bytes(self.cout, self.cin, ksize, prec))
         self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=srcs[0].device)
         self.cin_p = self.cout_p = 0
         self.sig = None
@@ -208,7 +213,13 @@ class _Packed:
         if self.pad is not None:
             src = self.pad.apply(src).contiguous()
         cin_p, cout_p = C.c_int32(0), C.c_int32(0)
-        if self.scaled:
+        if self.subpixel:
+            self.amax.zero_()
+            L.check(lib.sgd_weight_amax_subpixel(_ptr(src), self.cout, self.cin, _ptr(self.amax), stream), "sgd_weight_amax_subpixel")
+            L.check(lib.sgd_pack_weight_subpixel_scaled(_ptr(src), _ptr(self.buf), self.cout, self.cin, self.prec, _ptr(self.amax),
+                                                        _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p), stream),
+                    "sgd_pack_weight_subpixel_scaled")
+        elif self.scaled:
             self.amax.zero_()
             L.check(lib.sgd_weight_amax(_ptr(src), src.numel(), _ptr(self.amax), stream), "sgd_weight_amax")
             if len(self.srcs) == 1 and self.pad is None:
@@ -245,7 +256,7 @@ class _PackBatch:
         if hasattr(pk, "srcs"):                                   # unet._Packed
             if len(pk.srcs) != 1 or pk.pad is not None:
                 return None
-            p, t = pk.srcs[0], 0
+            p, t = pk.srcs[0], (L.PACK_SUBPIXEL if pk.subpixel else L.PACK_FORWARD)
             cout, cin = pk.cout, pk.cin
         else:                                                     # train._PackedAdj
             if len(pk.deps) != 1:
@@ -303,7 +314,7 @@ class _PackBatch:
             for pk, p, cp, op in self.members:                     # (fresh members were re-packed too: same bytes)
                 pk.cin_p, pk.cout_p = cp, op
                 pk.sig = ((p.data_ptr(), p._version),)
-                if hasattr(pk, "srcs") and pk.scaled:
+                if hasattr(pk, "srcs") and pk.scaled and not pk.subpixel:
                     AMAX_OF[p.data_ptr()] = (p._version, pk.amax, weakref.ref(p))
         for pk in self.packs:                                      # the rest, and small stale sets, one by one
             pk.refresh(stream)
@@ -606,10 +617,29 @@ class _Engine:
         (bf16x3 keeps the exact kernel: 8 mantissa bits per half do not hold the softmax weights)"""
         return self.lib.sgd_attention_split if self.prec == L.PREC_F16X3 else self.lib.sgd_attention
 
-    def pack(self, names, ksize, pad=None):
-        pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad)
+    def pack(self, names, ksize, pad=None, subpixel=False):
+        pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad, subpixel)
         self.packed.append(pk)
         return pk
+
+    def up_conv(self, tag, x0, c0, y, cout, wname, conv, *, stats=False, **kw):
+        """nearest-x2-upsample 3x3 conv (conv[6] == RS_UP2).  Returns the DIRECT RS_UP2 descriptor: the tape describes the layer
+        as the conv it is, and the backward's weight gradient re-stages the upsampled input from it.  Where
+        sgd_igemm_subpixel_ok allows (split modes, ...; SGDM_SUBPIXEL=0: never) the launch is the sub-pixel conv at the input
+        resolution -- 4 taps per output instead of 9 -- on a pack of its own; the descriptor is then not launched."""
+        assert conv[6] == L.RS_UP2
+        pk = self.pack([wname], 3)
+        q = L.IgemmArgs()
+        q.mode, (q.n, q.hi, q.wi, q.ho, q.wo, q.stride, q.resample) = L.MODE_CONV3, conv
+        q.c0, q.c1, q.cout, q.y_ld, q.prec = c0, kw.get("c1", 0), cout, cout, self.prec
+        q.stats = 1 if stats else 0                   # (not read: the launch wants statistics)
+        q.tune = L.TUNE_NO_SUBPIXEL if os.environ.get("SGDM_SUBPIXEL", "1") == "0" else 0
+        if kw.get("res") is not None or not self.lib.sgd_igemm_subpixel_ok(C.byref(q)):
+            return self.igemm(tag, x0, c0, y, cout, pk, conv=conv, stats=stats, **kw)
+        direct = self.igemm(tag, x0, c0, y, cout, pk, conv=conv, launch=False, **kw)
+        self.igemm(tag, x0, c0, y, cout, self.pack([wname], 3, subpixel=True), conv=conv[:6] + (L.RS_UP2_SUBPIXEL,),
+                   stats=stats, **kw)
+        return direct
 
     def padded(self, name, pad):
         """device copy of parameter `name` in a zero-padded layout (_Pad over its last dim for vectors / tables), kept in
@@ -681,7 +711,7 @@ class _Engine:
         # algorithmic work of this launch: 2*M*N*K flops; every input/output element moved once + weights
         rows = conv[0] * conv[3] * conv[4] if conv is not None else m
         rows_in = conv[0] * conv[1] * conv[2] if conv is not None else m
-        taps = 9 if conv is not None else 1
+        taps = (4 if conv[6] == L.RS_UP2_SUBPIXEL else 9) if conv is not None else 1
         cin = c0 + c1
         flops = 2.0 * rows * cout * taps * cin
         nbytes = 4.0 * (rows_in * cin + rows * cout * (2 if res is not None else 1) + taps * cin * cout)
@@ -836,9 +866,8 @@ class _Engine:
             elif kind == "up":
                 (t, c, hh, ww), = srcs
                 y = self.buf(self.n, hh * 2, ww * 2, c)
-                a = self.igemm(p + ".conv", t, c, y, c, self.pack([p + ".conv.weight"], 3),
-                               conv=(self.n, hh, ww, hh * 2, ww * 2, 1, L.RS_UP2), bias=self.m.P(p + ".conv.bias"),
-                               stats=True)
+                a = self.up_conv(p + ".conv", t, c, y, c, p + ".conv.weight",
+                                 (self.n, hh, ww, hh * 2, ww * 2, 1, L.RS_UP2), bias=self.m.P(p + ".conv.bias"), stats=True)
                 self.tape.append(dict(kind="up", p=p, x=t, y=y, c=c, hw_in=(hh, ww), a=a))
                 srcs = [(y, c, hh * 2, ww * 2)]
         return srcs[0]
@@ -859,9 +888,12 @@ class _Engine:
                          p + ".in_layers.0")
         sums1 = self._last_sums
         h1 = self.buf(n, ho, wo, cout)
-        ac1 = self.igemm(p + ".in_layers.2", t0, c0, h1, cout, self.pack([p + ".in_layers.2.weight"], 3), x1=t1,
-                         c1=c1, conv=(n, hh, ww, ho, wo, 1, rs), pro=L.PRO_AFFINE_NC, silu=1, pa=a1, pb=b1,
-                         bias=P(p + ".in_layers.2.bias"), stats=ss)
+        kw1 = dict(x1=t1, c1=c1, pro=L.PRO_AFFINE_NC, silu=1, pa=a1, pb=b1, bias=P(p + ".in_layers.2.bias"), stats=ss)
+        if rs == L.RS_UP2:
+            ac1 = self.up_conv(p + ".in_layers.2", t0, c0, h1, cout, p + ".in_layers.2.weight", (n, hh, ww, ho, wo, 1, rs), **kw1)
+        else:
+            ac1 = self.igemm(p + ".in_layers.2", t0, c0, h1, cout, self.pack([p + ".in_layers.2.weight"], 3),
+                             conv=(n, hh, ww, ho, wo, 1, rs), **kw1)
         film_ptr = self.film.data_ptr() + 4 * self.film_off[p]
         if ss:
             a2, b2 = self.gn(p + ".out_layers.0", [(h1, cout)], ho * wo, p + ".out_layers.0", film=film_ptr,

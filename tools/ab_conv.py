@@ -6,7 +6,10 @@ ABI 15; rounds are interleaved, median and min reported, outputs of all variants
 
     python tools/ab_conv.py --variants base=lib/libsgdm_hip_base.so new=lib/libsgdm_hip.so new256=lib/libsgdm_hip.so:tune=2 \
         --shapes 80,256,256,64 80,512,512,32 ... [--rounds 7] [--reps 20] [--prec f16x3] [--plain]
-shape = n,cin,cout,hw[,ks]"""
+shape = n,cin,cout,hw[,ks[,up]]: up = 1 -- the nearest-x2-upsample conv of a hw x hw input (ResBlock up / Upsample, no
+residual); a variant with `subpixel=1` runs it as the sub-pixel conv (SGD_RS_UP2_SUBPIXEL) on the sub-pixel pack:
+    --variants direct=lib/libsgdm_hip.so sub128=lib/libsgdm_hip.so:subpixel=1:tune=1 sub256=lib/libsgdm_hip.so:subpixel=1:tune=2 \
+    --shapes 80,512,512,16,3,1 80,256,256,32,3,1"""
 import argparse, ctypes as C, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "self-guided-diffusion-models_amd"))
@@ -41,6 +44,8 @@ WORK = {}
 for shp in a.shapes:
     f = [int(x) for x in shp.split(",")]
     n, cin, cout, hw = f[:4]; ks = f[4] if len(f) > 4 else 3
+    up = len(f) > 5 and f[5] == 1
+    ho = 2 * hw if up else hw
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(n, hw, hw, cin, device="cuda", generator=g)
     w = torch.randn(cout, cin, ks, ks, device="cuda", generator=g) / (cin * ks * ks) ** 0.5
@@ -48,29 +53,41 @@ for shp in a.shapes:
     pa, pb = 1 + 0.3 * torch.randn(n, cin, device="cuda", generator=g), 0.3 * torch.randn(n, cin, device="cuda", generator=g)
     runs = []
     for name, lib, env in variants:
-        buf = torch.empty(lib.sgd_packed_weight_bytes(cout, cin, ks, prec) // 4, device="cuda")
+        sub = up and env.get("subpixel") == "1"
         cp, op = C.c_int32(), C.c_int32()
-        L.check(lib.sgd_pack_weight(C.c_void_p(w.data_ptr()), C.c_void_p(buf.data_ptr()), cout, cin, ks, prec, C.byref(cp), C.byref(op), st), "pack")
-        y = torch.full((n, hw, hw, cout), float("nan"), device="cuda")
+        sinv = torch.ones(1, device="cuda")
+        if sub:                                              # the 16 summed kernels, scaled by max |V|
+            amax = torch.zeros(1, dtype=torch.int32, device="cuda")
+            buf = torch.empty(lib.sgd_packed_weight_subpixel_bytes(cout, cin, prec) // 4, device="cuda")
+            L.check(lib.sgd_weight_amax_subpixel(C.c_void_p(w.data_ptr()), cout, cin, C.c_void_p(amax.data_ptr()), st), "amax")
+            L.check(lib.sgd_pack_weight_subpixel_scaled(C.c_void_p(w.data_ptr()), C.c_void_p(buf.data_ptr()), cout, cin, prec,
+                                                        C.c_void_p(amax.data_ptr()), C.c_void_p(sinv.data_ptr()), C.byref(cp),
+                                                        C.byref(op), st), "pack")
+        else:
+            buf = torch.empty(lib.sgd_packed_weight_bytes(cout, cin, ks, prec) // 4, device="cuda")
+            L.check(lib.sgd_pack_weight(C.c_void_p(w.data_ptr()), C.c_void_p(buf.data_ptr()), cout, cin, ks, prec, C.byref(cp), C.byref(op), st), "pack")
+        y = torch.full((n, ho, ho, cout), float("nan"), device="cuda")
         q = L.IgemmArgs()
         q.x0, q.c0 = x.data_ptr(), cin
         if ks == 3:
-            q.mode, q.n, q.hi, q.wi, q.ho, q.wo, q.stride = L.MODE_CONV3, n, hw, hw, hw, hw, 1
+            q.mode, q.n, q.hi, q.wi, q.ho, q.wo, q.stride = L.MODE_CONV3, n, hw, hw, ho, ho, 1
+            q.resample = (L.RS_UP2_SUBPIXEL if sub else L.RS_UP2) if up else L.RS_NONE
+            q.w_scale_inv = sinv.data_ptr()
         else:
             q.mode, q.m, q.rows_per_n, q.stride = L.MODE_FLAT, n * hw * hw, hw * hw, 1
         if not a.plain:
             q.pro, q.pro_silu, q.pa, q.pb = L.PRO_AFFINE_NC, 1, pa.data_ptr(), pb.data_ptr()
-            q.res = res.data_ptr()
+            q.res = 0 if up else res.data_ptr()
         q.w, q.cin_p, q.cout_p, q.bias = buf.data_ptr(), cp.value, op.value, bias.data_ptr()
         q.y, q.cout, q.y_ld, q.prec = y.data_ptr(), cout, cout, prec
         q.tune, q.grid_cap = int(env.get("tune", 0)), int(env.get("grid_cap", 0))
-        env = {k: v for k, v in env.items() if k not in ("tune", "grid_cap")}     # (a copy: the variant serves every shape)
+        env = {k: v for k, v in env.items() if k not in ("tune", "grid_cap", "subpixel")}     # (a copy: the variant serves every shape)
         if hasattr(lib, "sgd_igemm_work_bytes"):            # balanced tail (tune=16 turns it off)
             wb = int(lib.sgd_igemm_work_bytes())
             if name not in WORK:
                 WORK[name] = torch.zeros(wb // 4, device="cuda")
             q.work, q.work_bytes = WORK[name].data_ptr(), wb
-        runs.append((name, lib, env, q, y, buf, []))
+        runs.append((name, lib, env, q, y, (buf, sinv), []))
 
     def launch(lib, env, q, reps):
         old = {k: os.environ.get(k) for k in env}
@@ -90,9 +107,9 @@ for shp in a.shapes:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); launch(lib, env, q, a.reps); e1.record(); torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1) / a.reps)
-    fl = 2.0 * n * hw * hw * cout * cin * ks * ks
+    fl = 2.0 * n * ho * ho * cout * cin * ks * ks          # (up: the direct conv's work -- fp32-equivalent for the sub-pixel form)
     ref = runs[0][4]
-    line = f"n={n} cin={cin} cout={cout} hw={hw} ks={ks}:"
+    line = f"n={n} cin={cin} cout={cout} hw={hw} ks={ks}{' up' if up else ''}:"
     for name, lib, env, q, y, buf, ts in runs:
         med, mn = statistics.median(ts), min(ts)
         diff = float((y - ref).abs().max() / ref.abs().max())

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch table of one UNet evaluation (HIP events around every launch).
-    python tools/profile_layers.py [--workload c2] [--prec f16x3] [--batch 40]"""
+    python tools/profile_layers.py [--workload c2] [--prec f16x3] [--batch 40] [--no-subpixel]
+--no-subpixel: the nearest-upsample 3x3 convs as direct SGD_RS_UP2 launches (SGDM_SUBPIXEL=0) instead of sub-pixel ones"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "self-guided-diffusion-models_amd"))
@@ -10,8 +11,10 @@ from sgdm_amd import _lib as L
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--workload", default="c2"); ap.add_argument("--prec", default="f16x3"); ap.add_argument("--batch", type=int, default=0)
-ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--reps", type=int, default=3); ap.add_argument("--no-subpixel", action="store_true")
 a = ap.parse_args()
+if a.no_subpixel:
+    os.environ["SGDM_SUBPIXEL"] = "0"
 wl = bench.WORKLOADS[a.workload]; B = a.batch or wl["batch"]
 dev = torch.device("cuda", 0)
 m, sd, data = bench.build_model(wl, dev, a.prec, B)
