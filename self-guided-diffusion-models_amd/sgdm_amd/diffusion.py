@@ -95,24 +95,50 @@ class _StepRunner:
         self.kwargs = dict(kwargs)
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
         self.lib = L.load()
+        self._drop = {}
+
+    def fused_cfg(self):
+        """whether a step takes the batch-doubled evaluation whose guided score is formed inside the step kernel: the
+        drop-in UNet, a numeric guidance weight that is not the model kind's single-evaluation 0 / 1 shortcut, no ``p0``"""
+        m, w = self.model, self.kwargs.get("cond_scale")
+        if m is None or not isinstance(w, (int, float)) or self.kwargs.get("p0") is not None:
+            return False
+        fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else True
+        return not (fast_int and w in (0, 1))
+
+    def drop_mask(self, B, dev):
+        """(whether the model reads a cond-drop mask at all, drop probabilities [2B] of the doubled batch: the conditional
+        half never, the unconditional half always)"""
+        if (B, dev) not in self._drop:              # formed once per trajectory, not per step
+            m = self.model
+            has_mask = (m._cond_width > 0) or (m._in_ch_total > m.in_channels)
+            self._drop[B, dev] = has_mask, torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), 1.0, device=dev)))
+        return self._drop[B, dev]
 
     def eps(self, x, t):
         """returns (eps tensor/engine buffer, cfg_mode, w, b, c) describing how the step kernel reads it"""
         B, Cc = x.shape[0], x.shape[1]
         m = self.model
-        if m is not None:
-            w = self.kwargs.get("cond_scale")
-            cond, layout = self.kwargs.get("cond"), self.kwargs.get("layout")
-            fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else isinstance(w, (int, float))
-            if isinstance(w, (int, float)) and not (fast_int and w in (0, 1)) and self.kwargs.get("p0") is None:
-                # batch-doubled evaluation, guided score formed inside the step kernel
-                has_mask = (m._cond_width > 0) or (m._in_ch_total > m.in_channels)
-                p = torch.cat((torch.full((B,), 0.0, device=x.device), torch.full((B,), 1.0, device=x.device)))
-                mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-                eng = m._run(x, t, cond, layout, mask, 2 * B)
-                return eng.eps_nhwc, m._scale_mode(), float(w), B, Cc
+        if self.fused_cfg():
+            has_mask, p = self.drop_mask(B, x.device)
+            mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
+            eng = m._run(x, t, self.kwargs.get("cond"), self.kwargs.get("layout"), mask, 2 * B)
+            return eng.eps_nhwc, m._scale_mode(), float(self.kwargs["cond_scale"]), B, Cc
         e = self.fn(x, t, **self.kwargs)            # generic path: guided eps, NCHW
         return e.contiguous(), 0, 0.0, B * Cc, 1
+
+
+def _start_image(shape, x_T, dev, copy=False):
+    """x_T: drawn, or the injected one as fp32 on the device (``copy``: a private one the sampler may update in place)"""
+    if x_T is None:
+        return torch.randn(shape, device=dev)
+    return x_T.to(dev, torch.float32, copy=copy).contiguous()
+
+
+def _t_rows(times, B, dev):
+    """[steps, B] long device table: row i is the UNet's time argument of schedule row i"""
+    t = torch.tensor(np.ascontiguousarray(times), dtype=torch.long, device=dev)
+    return t.view(-1, 1).expand(len(t), B).contiguous()
 
 
 class _GraphedStep:
@@ -129,9 +155,11 @@ class _GraphedStep:
     """
 
     MAX_PER_ENGINE = 8          # captured steps kept per (model, batch, resolution, precision) engine
+    COEF = (5, torch.float32)   # one row of the trajectory's table
+    NOISE = True                # the update reads a z
 
     @classmethod
-    def get(cls, runner, img, kind, clip, temperature=1.0):
+    def get(cls, runner, img, kind, clip, times, tab, temperature=1.0):
         """the captured step for this (model, batch, resolution, precision, guidance, sampler) -- built on first use and
         kept on the model, so later trajectories of the same configuration only refresh the static input buffers"""
         m, kw = runner.model, runner.kwargs
@@ -152,7 +180,7 @@ class _GraphedStep:
                 del cache[k]                                # oldest first (dicts keep insertion order): a sweep over
                                                             # guidance weights / temperatures must not grow without bound
             g = cache[key] = cls(runner, eng, img, kind, clip, temperature)
-        g.begin(img, cond, layout)
+        g.begin(img, cond, layout, times, tab)
         return g
 
     def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
@@ -163,8 +191,8 @@ class _GraphedStep:
         dev = img.device
         self.img = torch.empty_like(img)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
-        self.coef = torch.zeros(5, dtype=torch.float32, device=dev)
-        self.z = torch.empty_like(img)
+        self.coef = torch.zeros(self.COEF[0], dtype=self.COEF[1], device=dev)
+        self.z = torch.empty_like(img) if self.NOISE else None
         self.x0 = torch.empty_like(img)                 # clipped x0 prediction of the step (snapshot steps clone it)
         kw = runner.kwargs
         # static copies in exactly the dtypes the boundary kernels read (prepare() must not re-allocate them)
@@ -172,9 +200,8 @@ class _GraphedStep:
         self.cond = None if c0 is None else (c0.detach().clone() if c0.dtype == torch.int64 else c0.detach().float().clone()).contiguous()
         self.layout = None if l0 is None else (l0.detach().clone() if l0.dtype in (torch.uint8, torch.int32, torch.int64)
                                                else l0.detach().float().clone()).contiguous()
-        self.has_mask = (m._cond_width > 0) or (m._in_ch_total > m.in_channels)
+        self.has_mask, self.p = runner.drop_mask(B, dev)
         self.u = torch.zeros(2 * B, device=dev)
-        self.p = torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), 1.0, device=dev)))
         self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
         eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
         self._inputs = eng._keep_inputs                 # the captured launches read these buffers on every replay
@@ -204,67 +231,53 @@ class _GraphedStep:
                                                float(temperature), clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st),
                     "sgd_ddim_step_dev")
 
-    def begin(self, img, cond, layout):
-        """start of a trajectory: x_T and the guidance tensors into the static buffers; packed weights re-checked"""
+    def begin(self, img, cond, layout, times, tab):
+        """start of a trajectory: x_T, the guidance tensors and the trajectory's tables (UNet time and coefficient row per
+        schedule row) into device buffers; packed weights re-checked"""
         self.eng.refresh(torch.cuda.current_stream().cuda_stream)
         self.img.copy_(img)
         if self.cond is not None:
             self.cond.copy_(cond)
         if self.layout is not None:
             self.layout.copy_(layout)
+        self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
 
-    def step(self, t_row, coef_row, noise=None):
-        """t_row: [B] long device tensor; coef_row: device tensor [5]; draws the mask uniform and z like the eager path"""
+    def step(self, i, noise=None, want_x0=True):
+        """schedule row i; draws the mask uniform and z like the eager step (``x0`` is written on every replay)"""
         if self.has_mask:
             self.u.uniform_(0, 1)                       # prob_mask_like (openaimodel.py:462-463): same RNG consumption
             torch.lt(self.u, self.p, out=self.mask)
-        self.t.copy_(t_row)
-        if noise is None:
-            self.z.normal_()                            # == torch.randn(shape) (noise_like, util.py:264-267)
-        else:
+        self.t.copy_(self.ts[i])
+        if noise is not None:
             self.z.copy_(noise)
-        self.coef.copy_(coef_row)
+        elif self.NOISE:
+            self.z.normal_()                            # == torch.randn(shape) (noise_like, util.py:264-267)
+        self.coef.copy_(self.tab[i])
         self.graph.replay()
+
+    def final(self):
+        return self.img.clone()                         # the static buffer belongs to the cached graph
 
 
 class _GraphedPNDMStep(_GraphedStep):
     """The captured step of the PNDM sampler: UNet at 2B + ``sgd_pndm_step``.  Its static buffers are the Runge-Kutta
-    accumulator, the warm-up start image and the 3-slot eps history; ``row`` (include/sgdm_hip.h: sgd_pndm_row) says which
-    update the replay performs, so ONE graph serves warm-up and multistep evaluations alike.  No ``z`` is drawn: the only
-    RNG use per evaluation is the cond-drop mask's ``uniform_``, as in the reference (pndm_sampler.py:176-208)."""
+    accumulator, the warm-up start image and the 3-slot eps history; ``coef`` holds one ``sgd_pndm_row``
+    (include/sgdm_hip.h), which says which update the replay performs, so ONE graph serves warm-up and multistep
+    evaluations alike.  No ``z`` is drawn: the only RNG use per evaluation is the cond-drop mask's ``uniform_``, as in the
+    reference (pndm_sampler.py:176-208)."""
+
+    COEF = (8, torch.int32)
+    NOISE = False
 
     def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
         self.acc = torch.empty_like(img)
         self.base = torch.empty_like(img)
         self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
-        self.row = torch.zeros(8, dtype=torch.int32, device=img.device)
         super().__init__(runner, eng, img, kind, clip, temperature)
 
     def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
-        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.row), _ptr(self.acc),
+        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.coef), _ptr(self.acc),
                                        _ptr(self.base), _ptr(self.ring), B, Cc, hw, _ptr(img), st), "sgd_pndm_step")
-
-    def step(self, t_row, row):
-        """t_row: [B] long device tensor; row: [8] int32 device tensor (one sgd_pndm_row)"""
-        if self.has_mask:
-            self.u.uniform_(0, 1)                       # prob_mask_like: the eager path's only draw per evaluation
-            torch.lt(self.u, self.p, out=self.mask)
-        self.t.copy_(t_row)
-        self.row.copy_(row)
-        self.graph.replay()
-
-
-def _graph_ok(runner, sk, kwargs):
-    """the captured step covers the common case only: fused CFG evaluation on the drop-in UNet, a numeric guidance weight,
-    no noise dropout, no dynamic thresholding; ``hip_graph=False`` in the sampling kwargs turns it off"""
-    m = runner.model
-    w = runner.kwargs.get("cond_scale")
-    if m is None or not sk.get("hip_graph", True) or os.environ.get("SGDM_HIP_GRAPH", "1") == "0":
-        return False
-    fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else isinstance(w, (int, float))
-    if not isinstance(w, (int, float)) or (fast_int and w in (0, 1)) or runner.kwargs.get("p0") is not None:
-        return False
-    return sk.get("noise_dropout", 0) == 0 and sk.get("dtp", 1) >= 1.0
 
 
 def _quantile_rank(dtp, count):
@@ -273,6 +286,121 @@ def _quantile_rank(dtp, count):
     rank = torch.tensor(dtp, dtype=torch.float32) * (count - 1)
     lo = torch.floor(rank)
     return int(lo), int(torch.ceil(rank)), float(rank - lo)
+
+
+class _EagerStep:
+    """The same step launched kernel by kernel, with the captured step's surface (``step``, ``img``, ``x0``, ``final``).  It
+    covers what the capture leaves out: a generic ``denoise_sample_fn`` (guided NCHW eps), a given eps (PLMS), noise
+    dropout and dynamic thresholding.  RNG order per step as in the reference: the cond-drop ``uniform_`` inside the UNet
+    call, then ``z`` (drawn at eta = 0 too)."""
+
+    def __init__(self, runner, img, kind, clip, times, tab, sk, temperature=1.0):
+        self.runner, self.lib, self.kind, self.clip = runner, runner.lib, kind, clip
+        self.temperature = float(temperature)
+        B, Cc = img.shape[0], img.shape[1]
+        self.dims = B, Cc, int(np.prod(img.shape[2:]))
+        self.img, self.nxt, self.x0 = img, torch.empty_like(img), torch.empty_like(img)
+        assert tab.device.type == "cpu" and tab.dtype == torch.float32       # the kernels take a row as HOST floats
+        self.ts, self.tab = _t_rows(times, B, img.device), tab.contiguous()
+        self.noise_dropout = sk["noise_dropout"]
+        # dynamic thresholding (dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79): per-sample quantile of |x0|
+        self.rank = _quantile_rank(sk["dtp"], Cc * self.dims[2]) if sk.get("dtp", 1) < 1.0 else None
+        self.s_dyn = torch.empty(B, device=img.device)
+
+    def step(self, i, noise=None, want_x0=False, eps=None):
+        """schedule row i from ``img``; ``eps``: a guided NCHW eps to use instead of evaluating the UNet at ``ts[i]``"""
+        lib, img, (B, Cc, hw) = self.lib, self.img, self.dims
+        coef = C.cast(self.tab[i].data_ptr(), C.POINTER(C.c_float))
+        # a guided NCHW eps is "NHWC with one channel" over B*C planes
+        e, mode, w, bb, cc = self.runner.eps(img, self.ts[i]) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
+        z = torch.randn(img.shape, device=img.device) if noise is None else noise
+        if self.noise_dropout > 0.:
+            z = torch.nn.functional.dropout(z, p=self.noise_dropout)
+        x0, ddpm = self.x0 if want_x0 else None, self.kind == "ddpm"
+        if self.rank is not None:
+            # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C]
+            e4 = e if mode else e.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
+            L.check(lib.sgd_x0_quantile(0 if ddpm else 1, _ptr(img), _ptr(e4), mode, w, coef, B, Cc, hw, *self.rank,
+                                        _ptr(self.s_dyn), _stream()), "sgd_x0_quantile")
+            if ddpm:
+                L.check(lib.sgd_ddpm_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, _ptr(self.s_dyn), B, Cc, hw,
+                                              _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddpm_step_dyn")
+            else:
+                L.check(lib.sgd_ddim_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, self.temperature,
+                                              _ptr(self.s_dyn), B, Cc, hw, _ptr(self.nxt), _ptr(x0), _stream()),
+                        "sgd_ddim_step_dyn")
+        elif ddpm:
+            L.check(lib.sgd_ddpm_step(_ptr(img), _ptr(e), _ptr(z), mode, w, coef, self.clip, bb, cc, hw,
+                                      _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddpm_step")
+        else:
+            L.check(lib.sgd_ddim_step(_ptr(img), _ptr(e), _ptr(z), mode, w, coef, self.temperature, self.clip,
+                                      bb, cc, hw, _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddim_step")
+        self.img, self.nxt = self.nxt, img
+
+    def back(self):
+        """undo the last step's ping-pong: ``img`` is the image it started from, its result is left in ``nxt``"""
+        self.img, self.nxt = self.nxt, self.img
+
+    def final(self):
+        return self.img
+
+
+class _EagerPNDMStep:
+    """``_GraphedPNDMStep`` launched kernel by kernel; a new image per evaluation, as the reference's step returns"""
+
+    def __init__(self, runner, img, times, tab):
+        self.runner, self.img = runner, img
+        self.hw = int(np.prod(img.shape[2:]))
+        self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
+        self.acc, self.base = torch.empty_like(img), torch.empty_like(img)
+        self.ring = torch.empty((3,) + tuple(img.shape), device=img.device)
+
+    def step(self, i):
+        eps, mode, w, bb, cc = self.runner.eps(self.img, self.ts[i])
+        nxt = torch.empty_like(self.img)
+        L.check(self.runner.lib.sgd_pndm_step(_ptr(self.img), _ptr(eps), mode, w, _ptr(self.tab[i]), _ptr(self.acc),
+                                              _ptr(self.base), _ptr(self.ring), bb, cc, self.hw, _ptr(nxt), _stream()),
+                "sgd_pndm_step")
+        self.img = nxt
+
+    def final(self):
+        return self.img
+
+
+def _graph_ok(runner, sk):
+    """the captured step covers the common case only: fused CFG evaluation on the drop-in UNet, no noise dropout, no
+    dynamic thresholding; ``hip_graph=False`` in the sampling kwargs (or SGDM_HIP_GRAPH=0) turns it off"""
+    if not sk.get("hip_graph", True) or os.environ.get("SGDM_HIP_GRAPH", "1") == "0":
+        return False
+    return runner.fused_cfg() and sk.get("noise_dropout", 0) == 0 and sk.get("dtp", 1) >= 1.0
+
+
+def _sampler_step(runner, sk, img, kind, clip, times, tab, temperature=1.0):
+    """the step object a DDPM / DDIM loop walks its schedule with: captured where ``_graph_ok`` allows, else eager"""
+    if _graph_ok(runner, sk):
+        return _GraphedStep.get(runner, img, kind, clip, times, tab, temperature)
+    return _EagerStep(runner, img, kind, clip, times, tab, sk, temperature)
+
+
+class _Snapshots:
+    """the (x_inter, pred_x0) pairs a trajectory logs, at the schedule rows of linspace(0, total, log_num_per_prog); the
+    DDIM loop moves them to the host (ddim_plms_sampler.py:331-335), the others keep them on the device"""
+
+    def __init__(self, total, sk, host=False):
+        self.rows = torch.linspace(0, total, sk["log_num_per_prog"], dtype=torch.int).cpu().numpy().tolist()
+        self.host, self.inter, self.pred = host, [], []
+
+    def take(self, stepper):
+        for out, t in ((self.inter, stepper.img), (self.pred, stepper.x0)):
+            out.append((t.detach().cpu() if self.host else t.clone()).unsqueeze(0))
+
+    def result(self, stepper, shape):
+        """(final image, dict of the stacked snapshots -- [0, *shape] tensors when no visited row was a snapshot row)"""
+        img = stepper.final()
+        if not self.pred:
+            empty = img.new_zeros((0,) + tuple(shape), device="cpu" if self.host else None)
+            return img, dict(x_inter=empty, pred_x0=empty.clone())
+        return img, dict(x_inter=torch.cat(self.inter, 0), pred_x0=torch.cat(self.pred, 0))
 
 
 class Schedule_DDPM(nn.Module):
@@ -362,87 +490,42 @@ class Schedule_DDPM(nn.Module):
             return {}
         return vis_schedule_ddpm(_betas=self.betas.cpu(), _alphas_cumprod=self.alphas_cumprod.cpu(), _snr_derivative=None)
 
+    def step_table(self, temperature):
+        """[T, 5] fp32 rows of sgd_ddpm_step for one trajectory: ``_step_tab`` with the noise scale times the per-step
+        temperature (product formed in double, then rounded to fp32) and no noise at t == 0"""
+        tab = self._step_tab.double()
+        if self.hparams.parameterization == "x0":
+            tab[:, 0], tab[:, 1] = 0.0, -1.0        # x_recon = model_out (ddpm_sampler.py:160-161): 0*x - (-1)*out, exact
+        tab[:, 4] *= torch.tensor([float(v) for v in temperature], dtype=torch.float64)
+        tab[0, 4] = 0.0
+        return tab.float()
+
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, denoise_sample_fn=None, denoise_sample_fn_kwargs=None, **kwargs):
         """ancestral DDPM loop (ddpm_sampler.py:194-238); ``x_T`` / ``noise_fn(i)`` may be injected for tests"""
         sk = sampling_kwargs
-        temperature, noise_dropout = sk["temperature"], sk["noise_dropout"]
-        timesteps = sk["num_timesteps"]
+        temperature, timesteps = sk["temperature"], sk["num_timesteps"]
         h = self.hparams
         self.register_schedule(timesteps=timesteps, given_betas=h.given_betas, beta_schedule=h.beta_schedule,
                                linear_start=h.linear_start, linear_end=h.linear_end, cosine_s=h.cosine_s)
-        dyn = sk.get("dtp", 1) < 1.0            # dynamic thresholding (diffusion_utils/util.py:70-79)
         if h.parameterization not in ("eps", "x0"):
             raise NotImplementedError()                                        # ddpm_sampler.py:162-163
-        x0_param = h.parameterization == "x0"
         dev = self.betas.device
-        B, Cc = shape[0], shape[1]
-        hw = int(np.prod(shape[2:]))
-        x_T = kwargs.get("x_T")
-        img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev).float().contiguous()
+        img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         if type(temperature) == float or isinstance(temperature, int):
             temperature = [float(temperature)] * timesteps
-        snaps = torch.linspace(0, timesteps, sk["log_num_per_prog"], dtype=torch.int).cpu().numpy().tolist()
+        snaps = _Snapshots(timesteps, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
-        lib = runner.lib
-        ts_tab = torch.arange(timesteps, device=dev, dtype=torch.long).view(-1, 1).expand(timesteps, B).contiguous()
-        pred, inter = [], []
-        clip = 1 if sk["clip_denoised"] else 0
-        coef = (C.c_float * 5)()
-        nxt = torch.empty_like(img)
+        stepper = _sampler_step(runner, sk, img, "ddpm", 1 if sk["clip_denoised"] else 0, range(timesteps),
+                                self.step_table(temperature))
         order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
-        order = list(reversed(range(0, timesteps))) if order is None else list(order)
-        gstep, coef_dev = None, None
-        if _graph_ok(runner, sk, kwargs):
-            tab = self._step_tab.double()                                       # same double product -> fp32 as below
-            if x0_param:
-                tab[:, 0], tab[:, 1] = 0.0, -1.0
-            tab[:, 4] *= torch.tensor([float(v) for v in temperature], dtype=torch.float64)
-            tab[0, 4] = 0.0                                                     # no noise when t == 0
-            coef_dev = tab.float().to(dev)
-            gstep = _GraphedStep.get(runner, img, "ddpm", clip)
-            img = gstep.img                                                     # updated in place by the replays
-        for i in order:
-            ts = ts_tab[i]
-            want = i in snaps
-            if gstep is not None:
-                gstep.step(ts, coef_dev[i], None if noise_fn is None else noise_fn(i).to(dev))
-                if want:
-                    pred.append(gstep.x0.clone().unsqueeze(0))
-                    inter.append(img.clone().unsqueeze(0))
-                continue
-            eps, mode, w, bb, cc = runner.eps(img, ts)
-            z = torch.randn(shape, device=dev) if noise_fn is None else noise_fn(i).to(dev)
-            if noise_dropout > 0.:
-                z = torch.nn.functional.dropout(z, p=noise_dropout)
-            row = self._step_tab[i]
-            coef[0], coef[1], coef[2], coef[3] = row[0], row[1], row[2], row[3]
-            if x0_param:
-                coef[0], coef[1] = 0.0, -1.0        # x_recon = model_out (ddpm_sampler.py:160-161): 0*x - (-1)*out, exact
-            coef[4] = (float(row[4]) * float(temperature[i])) if i != 0 else 0.0      # no noise when t == 0
-            x0 = torch.empty_like(img) if want else None
-            if dyn:
-                lo, hi, frac = _quantile_rank(sk["dtp"], Cc * hw)
-                s_dyn = torch.empty(B, device=dev)
-                # the step kernels see a guided NCHW eps as (B*C) one-channel planes; the quantile is per SAMPLE
-                e4 = eps if mode else eps.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
-                L.check(lib.sgd_x0_quantile(0, _ptr(img), _ptr(e4), mode, w, coef, B, Cc, hw, lo, hi, frac, _ptr(s_dyn),
-                                            _stream()), "sgd_x0_quantile")
-                L.check(lib.sgd_ddpm_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, _ptr(s_dyn), B, Cc, hw,
-                                              _ptr(nxt), _ptr(x0), _stream()), "sgd_ddpm_step_dyn")
-            else:
-                L.check(lib.sgd_ddpm_step(_ptr(img), _ptr(eps), _ptr(z), mode, w, coef, clip, bb, cc, hw,
-                                          _ptr(nxt), _ptr(x0), _stream()), "sgd_ddpm_step")
-            img, nxt = nxt, img
+        for i in (reversed(range(0, timesteps)) if order is None else order):
+            want = i in snaps.rows
+            stepper.step(i, None if noise_fn is None else noise_fn(i).to(dev), want)
             if want:
-                pred.append(x0.unsqueeze(0))
-                inter.append(img.clone().unsqueeze(0))
-        if gstep is not None:
-            img = img.clone()                       # the static buffer belongs to the cached graph
-        if not pred:
-            return img, dict(pred_x0=img.new_zeros((0,) + tuple(shape)), x_inter=img.new_zeros((0,) + tuple(shape)))
-        return img, dict(pred_x0=torch.cat(pred, 0), x_inter=torch.cat(inter, 0))
+                snaps.take(stepper)
+        return snaps.result(stepper, shape)
 
 
 class DDIMSampler(object):
@@ -463,6 +546,10 @@ class DDIMSampler(object):
         sig, a, ap = make_ddim_sampling_parameters(ac.detach().float().cpu(), self.ddim_timesteps, eta)
         self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sig, a, ap
         self.ddim_sqrt_one_minus_alphas = np.sqrt(1.0 - a)
+        # [S, 5] fp32 rows of sgd_ddim_step (the fifth column, the DDPM rows' noise scale, stays 0): the table entries cast
+        # to fp32 as torch.full_like(x, table[index]) does (ddim_plms_sampler.py:360-366)
+        tab = np.stack([self.ddim_sqrt_one_minus_alphas, a, ap, sig, np.zeros_like(sig)], 1)
+        self.step_table = torch.tensor(tab, dtype=torch.float64).float()
 
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, **kwargs):
@@ -476,93 +563,59 @@ class DDIMSampler(object):
     @torch.no_grad()
     def plms_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, **kwargs):
         """ddim_plms_sampler.py:394-482: pseudo linear multistep.  Per step ONE UNet evaluation at 2B (two on the
-        first step), the guided eps kept as a [B,3,H,W] tensor for the Adams-Bashforth history, and the same fused
-        update kernel as DDIM (p_sample_plms == p_sample_ddim with a given eps, ddim_plms_sampler.py:484-525).
+        first step), the guided eps kept as a [B,3,H,W] tensor for the Adams-Bashforth history, and the eager DDIM step
+        given that eps (p_sample_plms == p_sample_ddim with a given eps, ddim_plms_sampler.py:484-525); no captured step.
         RNG order of the reference: x_T, then one randn per p_sample_plms call (num_steps + 1 draws)."""
         sk = sampling_kwargs
-        dyn = sk.get("dtp", 1) < 1.0                             # ddim_plms_sampler.py:505-512 (same helper as ddim)
         dev = torch.device(self.device)
-        B, Cc = shape[0], shape[1]
-        hw = int(np.prod(shape[2:]))
-        x_T = kwargs.get("x_T")
-        img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev).float().contiguous()
+        img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
-        timesteps = self.ddim_timesteps
-        total = timesteps.shape[0]
-        time_range = np.flip(timesteps)
-        snaps = torch.linspace(0, total, sk["log_num_per_prog"], dtype=torch.int).cpu().numpy().tolist()
+        total = self.ddim_timesteps.shape[0]
+        snaps = _Snapshots(total, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
-        lib = runner.lib
-        clip = 1 if sk["clip_denoised"] else 0
-        coef = (C.c_float * 4)()
-        draws = [0]
+        stepper = _EagerStep(runner, img, "ddim", 1 if sk["clip_denoised"] else 0, self.ddim_timesteps, self.step_table, sk,
+                             float(sk["temperature"]))
+        B, Cc, hw = stepper.dims
+        draws = iter(range(total + 1))
 
         def guided(x, ts):
             eps, mode, w, bb, cc = runner.eps(x, ts)
             if mode == 0:
                 return eps.reshape(shape).clone()
             out = torch.empty(shape, device=dev)
-            L.check(lib.sgd_cfg_combine(_ptr(eps), mode, w, bb, cc, hw, _ptr(out), _stream()), "sgd_cfg_combine")
+            L.check(runner.lib.sgd_cfg_combine(_ptr(eps), mode, w, bb, cc, hw, _ptr(out), _stream()), "sgd_cfg_combine")
             return out
 
-        def update(x, e, index, want_x0):
-            z = torch.randn(shape, device=dev) if noise_fn is None else noise_fn(draws[0]).to(dev)
-            draws[0] += 1
-            if sk["noise_dropout"] > 0.0:
-                z = torch.nn.functional.dropout(z, p=sk["noise_dropout"])
-            coef[0] = float(self.ddim_sqrt_one_minus_alphas[index])
-            coef[1] = float(self.ddim_alphas[index])
-            coef[2] = float(self.ddim_alphas_prev[index])
-            coef[3] = float(self.ddim_sigmas[index])
-            nxt = torch.empty_like(x)
-            x0 = torch.empty_like(x) if want_x0 else None
-            if dyn:
-                lo, hi, frac = _quantile_rank(sk["dtp"], Cc * hw)
-                s_dyn = torch.empty(B, device=dev)
-                e4 = e.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
-                L.check(lib.sgd_x0_quantile(1, _ptr(x), _ptr(e4), 0, 0.0, coef, B, Cc, hw, lo, hi, frac, _ptr(s_dyn),
-                                            _stream()), "sgd_x0_quantile")
-                L.check(lib.sgd_ddim_step_dyn(_ptr(x), _ptr(e4), _ptr(z), 0, 0.0, coef, float(sk["temperature"]),
-                                              _ptr(s_dyn), B, Cc, hw, _ptr(nxt), _ptr(x0), _stream()), "sgd_ddim_step_dyn")
-                return nxt, x0
-            e = e.contiguous()
-            # a guided NCHW eps is "NHWC with one channel" over B*C planes
-            L.check(lib.sgd_ddim_step(_ptr(x), _ptr(e), _ptr(z), 0, 0.0, coef, float(sk["temperature"]), clip,
-                                      B * Cc, 1, hw, _ptr(nxt), _ptr(x0), _stream()), "sgd_ddim_step")
-            return nxt, x0
+        def noise():
+            return None if noise_fn is None else noise_fn(next(draws)).to(dev)
 
-        old_eps, pred, inter = [], [], []
-        for i, step in enumerate(time_range):
-            index = total - i - 1
-            ts = torch.full((B,), int(step), device=dev, dtype=torch.long)
-            e_t = guided(img, ts)
+        old_eps = []
+        for index in reversed(range(total)):
+            e_t = guided(stepper.img, stepper.ts[index])
             if len(old_eps) == 0:
-                ts_next = torch.full((B,), int(time_range[min(i + 1, len(time_range) - 1)]), device=dev, dtype=torch.long)
-                x_prev, _ = update(img, e_t, index, False)
-                e_t_prime = (e_t + guided(x_prev, ts_next)) / 2
+                stepper.step(index, noise(), eps=e_t)                   # x_prev of the plain step, only to evaluate eps at
+                e_t_prime = (e_t + guided(stepper.img, stepper.ts[max(index - 1, 0)])) / 2
+                stepper.back()
             elif len(old_eps) == 1:
                 e_t_prime = (3 * e_t - old_eps[-1]) / 2
             elif len(old_eps) == 2:
                 e_t_prime = (23 * e_t - 16 * old_eps[-1] + 5 * old_eps[-2]) / 12
             else:
                 e_t_prime = (55 * e_t - 59 * old_eps[-1] + 37 * old_eps[-2] - 9 * old_eps[-3]) / 24
-            want = index in snaps
-            img, x0 = update(img, e_t_prime, index, want)
+            want = index in snaps.rows
+            stepper.step(index, noise(), want, eps=e_t_prime)
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
             if want:
-                inter.append(img.unsqueeze(0))
-                pred.append(x0.unsqueeze(0))
-        return img, dict(x_inter=torch.cat(inter, 0), pred_x0=torch.cat(pred, 0))
+                snaps.take(stepper)
+        return snaps.result(stepper, shape)
 
     @torch.no_grad()
     def ddim_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, **kwargs):
         sk = sampling_kwargs
-        dyn = sk.get("dtp", 1) < 1.0
         dev = torch.device(self.device)
-        x_T = kwargs.get("x_T")
-        img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev).float().contiguous()
+        img = _start_image(shape, kwargs.get("x_T"), dev)
         dkw = dict(denoise_sample_fn_kwargs or {})
         vis = sk.get("vis")
         vis_noise = kwargs.get("vis_noise")                     # tests: the start noise a `vis` branch would draw
@@ -602,71 +655,21 @@ class DDIMSampler(object):
             dkw["cond"] = dkw["cond"][:ns].repeat_interleave(2, 0)
             assert len(dkw["cond"]) == len(img)
             dkw["p0"] = torch.tensor([1, 0], device=dev, dtype=torch.float32).repeat(ns)
-        denoise_sample_fn_kwargs = dkw
         shape = tuple(img.shape)
-        B, Cc = shape[0], shape[1]
-        hw = int(np.prod(shape[2:]))
         noise_fn = kwargs.get("noise_fn")
-        timesteps = self.ddim_timesteps
-        total = timesteps.shape[0]
-        snaps = torch.linspace(0, total, sk["log_num_per_prog"], dtype=torch.int).cpu().numpy().tolist()
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
-        lib = runner.lib
-        pred, inter = [], []
-        clip = 1 if sk["clip_denoised"] else 0
-        coef = (C.c_float * 4)()
-        nxt = torch.empty_like(img)
-        gstep, coef_dev = None, None
-        if _graph_ok(runner, sk, kwargs):
-            tab = np.stack([self.ddim_sqrt_one_minus_alphas, self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
-                            np.zeros_like(self.ddim_sigmas)], 1)
-            coef_dev = torch.tensor(tab, dtype=torch.float64).float().to(dev)   # float(table[index]) -> fp32, as below
-            gstep = _GraphedStep.get(runner, img, "ddim", clip, temperature=float(sk["temperature"]))
-            img = gstep.img
-            ts_dev = torch.tensor(np.ascontiguousarray(timesteps), dtype=torch.long, device=dev).view(-1, 1).expand(total, B).contiguous()
+        total = self.ddim_timesteps.shape[0]
+        snaps = _Snapshots(total, sk, host=True)
+        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw), sk, img, "ddim", 1 if sk["clip_denoised"] else 0,
+                                self.ddim_timesteps, self.step_table, float(sk["temperature"]))
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
-        walk = list(enumerate(np.flip(timesteps))) if visit is None else [(total - int(ix) - 1, timesteps[int(ix)]) for ix in visit]
-        for i, step in walk:
-            index = total - i - 1
-            want = index in snaps
-            if gstep is not None:
-                gstep.step(ts_dev[index], coef_dev[index], None if noise_fn is None else noise_fn(i).to(dev))
-                if want:
-                    inter.append(img.detach().cpu().unsqueeze(0))
-                    pred.append(gstep.x0.detach().cpu().unsqueeze(0))
-                continue
-            ts = torch.full((B,), int(step), device=dev, dtype=torch.long)
-            eps, mode, w, bb, cc = runner.eps(img, ts)
-            z = torch.randn(shape, device=dev) if noise_fn is None else noise_fn(i).to(dev)    # drawn even at eta=0
-            if sk["noise_dropout"] > 0.0:
-                z = torch.nn.functional.dropout(z, p=sk["noise_dropout"])
-            # torch.full_like(x, table[index]) casts the table entry to fp32 (ddim_plms_sampler.py:360-366)
-            coef[0] = float(self.ddim_sqrt_one_minus_alphas[index])
-            coef[1] = float(self.ddim_alphas[index])
-            coef[2] = float(self.ddim_alphas_prev[index])
-            coef[3] = float(self.ddim_sigmas[index])
-            x0 = torch.empty_like(img) if want else None
-            if dyn:
-                lo, hi, frac = _quantile_rank(sk["dtp"], Cc * hw)
-                s_dyn = torch.empty(B, device=dev)
-                e4 = eps if mode else eps.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
-                L.check(lib.sgd_x0_quantile(1, _ptr(img), _ptr(e4), mode, w, coef, B, Cc, hw, lo, hi, frac, _ptr(s_dyn),
-                                            _stream()), "sgd_x0_quantile")
-                L.check(lib.sgd_ddim_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, float(sk["temperature"]),
-                                              _ptr(s_dyn), B, Cc, hw, _ptr(nxt), _ptr(x0), _stream()), "sgd_ddim_step_dyn")
-            else:
-                L.check(lib.sgd_ddim_step(_ptr(img), _ptr(eps), _ptr(z), mode, w, coef, float(sk["temperature"]), clip,
-                                          bb, cc, hw, _ptr(nxt), _ptr(x0), _stream()), "sgd_ddim_step")
-            img, nxt = nxt, img
+        for index in (reversed(range(total)) if visit is None else map(int, visit)):
+            want = index in snaps.rows
+            # noise_fn counts the steps of a full walk (total - index - 1); z is drawn even at eta = 0
+            stepper.step(index, None if noise_fn is None else noise_fn(total - index - 1).to(dev), want)
             if want:
-                inter.append(img.detach().cpu().unsqueeze(0))
-                pred.append(x0.detach().cpu().unsqueeze(0))
-        if gstep is not None:
-            img = img.clone()                       # the static buffer belongs to the cached graph
-        if not pred:
-            return img, dict(x_inter=img.new_zeros((0,) + tuple(shape)).cpu(), pred_x0=img.new_zeros((0,) + tuple(shape)).cpu())
-        return img, dict(x_inter=torch.cat(inter, 0), pred_x0=torch.cat(pred, 0))
+                snaps.take(stepper)
+        return snaps.result(stepper, shape)
 
 
 PNDM_RK0, PNDM_RK12, PNDM_RK3, PNDM_PLMS = 0, 1, 2, 3            # include/sgdm_hip.h: SGD_PNDM_*
@@ -746,31 +749,17 @@ class PNDM_Sampler(object):
             warnings.warn("according to the PNDM paper, most gains can be reaped when timestep<250, so it is not "
                           "meaningful to set a timestep larger than 250")
         dev = torch.device(self.device)
-        B, Cc = shape[0], shape[1]
-        hw = int(np.prod(shape[2:]))
-        x_T = kwargs.get("x_T")
-        # a private copy: the trajectory is updated in place below / in the captured step
-        img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32, copy=True).contiguous()
+        # a private copy: the trajectory is updated in place in the captured step
+        img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
-        lib = runner.lib
-        tab_dev = tab.to(dev)
         # PNDM ignores dtp and noise_dropout: only the model / guidance conditions of the captured step apply
-        if _graph_ok(runner, dict(sk, noise_dropout=0, dtp=1), kwargs):
-            g = _GraphedPNDMStep.get(runner, img, "pndm", 0)
-            ts_dev = torch.tensor(times, dtype=torch.long, device=dev).view(-1, 1).expand(len(times), B).contiguous()
-            for k in range(len(times)):
-                g.step(ts_dev[k], tab_dev[k])
-            img = g.img.clone()                     # the static buffer belongs to the cached graph
-            return img, dict(pred_x0=img)
-        acc, base = torch.empty_like(img), torch.empty_like(img)
-        ring = torch.empty((3,) + tuple(img.shape), device=dev)
-        for k, t in enumerate(times):
-            ts = torch.full((B,), t, device=dev, dtype=torch.long)
-            eps, mode, w, bb, cc = runner.eps(img, ts)
-            nxt = torch.empty_like(img)             # a new image per evaluation, as the reference's step returns
-            L.check(lib.sgd_pndm_step(_ptr(img), _ptr(eps), mode, w, _ptr(tab_dev[k]), _ptr(acc), _ptr(base), _ptr(ring),
-                                      bb, cc, hw, _ptr(nxt), _stream()), "sgd_pndm_step")
-            img = nxt
+        if _graph_ok(runner, dict(sk, noise_dropout=0, dtp=1)):
+            stepper = _GraphedPNDMStep.get(runner, img, "pndm", 0, times, tab)
+        else:
+            stepper = _EagerPNDMStep(runner, img, times, tab)
+        for k in range(len(times)):
+            stepper.step(k)
+        img = stepper.final()
         return img, dict(pred_x0=img)
 
 
