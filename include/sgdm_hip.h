@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SGD_ABI_VERSION 23
+#define SGD_ABI_VERSION 24
 int sgd_abi_version(void);
 /* 16 hex digits identifying the sources and flags the library was compiled from (build.py: source_id()); static storage.
  * __graft_entry__.build() and tests/test_boundary_cpu.py compare it with the tree on disk. */
@@ -49,7 +49,11 @@ enum { SGD_RS_NONE = 0, SGD_RS_AVGPOOL2 = 1, SGD_RS_UP2 = 2,
         * channel counts, no residual, no dropout -- sgd_igemm_subpixel_ok(args) says whether a launch qualifies */
        SGD_RS_UP2_SUBPIXEL = 4 };
 enum { SGD_PRO_NONE = 0, SGD_PRO_AFFINE_NC = 1, SGD_PRO_LN_ROW = 2 };
-enum { SGD_PREC_F32 = 0, SGD_PREC_F16X3 = 1, SGD_PREC_BF16X3 = 2 };
+/* SGD_PREC_F16 / SGD_PREC_BF16 (ABI 24): INFERENCE-ONLY single-product modes -- x (after the fused prologue) and w are rounded once
+ * to IEEE half / bfloat16 (round to nearest even), one MFMA product per term, fp32 accumulate; everything outside the MFMA
+ * operands stays fp32.  They take the split modes' launch rules (16x16x32 form, sub-pixel convs, per-tensor weight scale), a packed
+ * weight is half the bytes of a split mode's, and the backward entry points refuse them (SGD_ERR_ARG). */
+enum { SGD_PREC_F32 = 0, SGD_PREC_F16X3 = 1, SGD_PREC_BF16X3 = 2, SGD_PREC_F16 = 3, SGD_PREC_BF16 = 4 };
 
 typedef struct sgd_igemm_args {
     /* input: channels [0,c0) from x0, [c0,c0+c1) from x1 (x1 may be NULL with c1 = 0) */

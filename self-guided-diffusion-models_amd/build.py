@@ -70,7 +70,10 @@ def source_id():
 NOPK = ["-DSGDM_IGEMM_NOPK", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 VARIANTS = {"igemm.hip": [("_f32", ["-DSGDM_IGEMM_PREC=0"]), ("_f16x3", ["-DSGDM_IGEMM_PREC=1"]),
                           ("_bf16x3", ["-DSGDM_IGEMM_PREC=2"]), ("_f16x3_nopk", ["-DSGDM_IGEMM_PREC=1", *NOPK]),
-                          ("_bf16x3_nopk", ["-DSGDM_IGEMM_PREC=2", *NOPK])]}
+                          ("_bf16x3_nopk", ["-DSGDM_IGEMM_PREC=2", *NOPK]),
+                          # single-product inference modes (include/sgdm_hip.h: SGD_PREC_F16 / SGD_PREC_BF16)
+                          ("_f16", ["-DSGDM_IGEMM_PREC=3"]), ("_bf16", ["-DSGDM_IGEMM_PREC=4"]),
+                          ("_f16_nopk", ["-DSGDM_IGEMM_PREC=3", *NOPK]), ("_bf16_nopk", ["-DSGDM_IGEMM_PREC=4", *NOPK])]}
 
 
 def _units():

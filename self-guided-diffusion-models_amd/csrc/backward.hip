@@ -1877,6 +1877,8 @@ static int wgrad_impl(const sgd_igemm_args* fwd, const float* gy, int32_t gy_ld,
                       int32_t ksplit, float* bias_slabs, void* scratch, int64_t scratch_bytes, void* stream) {
     SGD_CLEAR_ERR();
     if (!fwd || !gy || !slabs || cout <= 0 || ksplit <= 0 || gy_ld < cout) return SGD_ERR_ARG;
+    // the single-product modes (SGD_PREC_F16 / SGD_PREC_BF16) are inference only: no weight gradient is built for them
+    if (fwd->prec < SGD_PREC_F32 || fwd->prec > SGD_PREC_BF16X3) return SGD_ERR_ARG;
     WArgs w;
     w.a = *fwd;
     w.no_flat_pipe = (fwd->tune & SGD_TUNE_WGRAD_NO_PIPE) ? 1 : 0;

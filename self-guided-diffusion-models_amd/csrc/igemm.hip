@@ -23,6 +23,8 @@
 //             PREC_F16X3 / BF16X3 split every operand x = hi + lo into two 16-bit floats and
 //             accumulate lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_{f16,bf16} in fp32
 //             (BASELINE.md section 2 "precision headroom": 4.3e-6 / 2.6e-5 rel. error per UNet eval).
+//             PREC_F16 / BF16 (inference only) round every operand ONCE to a 16-bit float and issue the hi * hi product
+//             alone: one MFMA per stage, no lo half in the LDS rows or in the packed weights (half-size units, wunit()).
 //
 // Replaces (reference): nn.Conv2d/Conv1d/Linear call sites listed in include/sgdm_hip.h.
 #include <type_traits>
@@ -79,10 +81,20 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // F32   : row = 32 floats (channel order) + 4 pad.
 // split : row = 4 groups of 8 channels; group = hi[8] (16 B) | lo[8] (16 B); + 16 B pad. Same 144 B.
+// single: the split row without its lo halves -- group = hi[8] (16 B) | 16 B never written or read: 64 B of payload per row at the
+//         split modes' addresses, so the conflict-free ds_read_b128 lane maps (pixel_of_lane) hold unchanged; half the LDS
+//         write and read traffic per chunk.
 template <int PREC>
 __device__ __forceinline__ void lds_store_act(float* rowp, int c4, f32x4 v) {
     if constexpr (PREC == SGD_PREC_F32) {
         *reinterpret_cast<f32x4*>(rowp + c4 * 4) = v;
+    } else if constexpr (PREC == SGD_PREC_F16) {
+        _Float16* base = reinterpret_cast<_Float16*>(rowp) + (c4 >> 1) * 16 + (c4 & 1) * 4;
+        *reinterpret_cast<u32x2*>(base) = round4_f16(v);
+    } else if constexpr (PREC == SGD_PREC_BF16) {
+        typedef __bf16 T4 __attribute__((ext_vector_type(4)));
+        __bf16* base = reinterpret_cast<__bf16*>(rowp) + (c4 >> 1) * 16 + (c4 & 1) * 4;
+        *reinterpret_cast<T4*>(base) = T4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
     } else if constexpr (PREC == SGD_PREC_F16X3) {
         // channels c4*4 .. +3 -> group g = c4 >> 1, position (c4 & 1) * 4 inside the 8-group (2-byte elements)
         _Float16* base = reinterpret_cast<_Float16*>(rowp) + (c4 >> 1) * 16 + (c4 & 1) * 4;
@@ -107,19 +119,25 @@ __device__ __forceinline__ void lds_store_act(float* rowp, int c4, f32x4 v) {
 // MFMA operand fragments.  AU: the input side (pixels) of ONE stage = one 32-row block x one K sub-step, read from the LDS
 // tile; B: the weight side of one K sub-step for the wave's NT 32-column blocks, loaded from the fragment-ordered packed
 // weights in global memory (`p` already carries lane * 16).  A stage multiplies one AU into NT accumulator tiles.
+// bytes of one packed weight unit (32 output x 32 input channels of one tap) and of one of its two 16-channel sub-steps: the
+// single-product modes carry no lo half (pack.hip)
+template <int PREC> constexpr int wunit() { return prec_single(PREC) ? WUNIT / 2 : WUNIT; }
+template <int PREC> constexpr int wsub() { return prec_single(PREC) ? 1024 : 2048; }
+
 template <int PREC, int NT> struct Frag {
     typedef typename Split<PREC>::T T;
     typedef T T8 __attribute__((ext_vector_type(8)));
+    static constexpr bool ONE = prec_single(PREC);    // hi * hi alone: the lo members below are never touched
     static constexpr int NKS = KC / 16;           // 16 channels per sub-step
-    static constexpr int NREADS = 2;              // ds_read_b128 per stage
-    static constexpr int NWLOADS = 2 * NT;        // 16-byte global loads per sub-step
-    static constexpr int NMMA = 3 * NT;           // MFMAs per stage
+    static constexpr int NREADS = ONE ? 1 : 2;    // ds_read_b128 per stage
+    static constexpr int NWLOADS = (ONE ? 1 : 2) * NT;   // 16-byte global loads per sub-step
+    static constexpr int NMMA = (ONE ? 1 : 3) * NT;      // MFMAs per stage
     struct AU {
         T8 h, l;
         __device__ __forceinline__ void load(const float* rowp, int ks, int lh) {
             const int goff = (ks * 2 + lh) * 8;   // float offset of this lane-half's 8-channel group
             h = *reinterpret_cast<const T8*>(rowp + goff);
-            l = *reinterpret_cast<const T8*>(rowp + goff + 4);
+            if constexpr (!ONE) l = *reinterpret_cast<const T8*>(rowp + goff + 4);
         }
     };
     struct B {
@@ -127,15 +145,19 @@ template <int PREC, int NT> struct Frag {
         __device__ __forceinline__ void load(const char* p, int ks) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                h[nt] = *reinterpret_cast<const T8*>(p + nt * WUNIT + ks * 2048);
-                l[nt] = *reinterpret_cast<const T8*>(p + nt * WUNIT + ks * 2048 + 1024);
+                h[nt] = *reinterpret_cast<const T8*>(p + nt * wunit<PREC>() + ks * wsub<PREC>());
+                if constexpr (!ONE) l[nt] = *reinterpret_cast<const T8*>(p + nt * WUNIT + ks * 2048 + 1024);
             }
         }
     };
     static __device__ __forceinline__ void mma(f32x16 (&acc)[NT], const AU& a, const B& b) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if constexpr (PREC == SGD_PREC_F16X3) {
+            if constexpr (PREC == SGD_PREC_F16) {
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b.h[nt], a.h, acc[nt], 0, 0, 0);
+            } else if constexpr (PREC == SGD_PREC_BF16) {
+                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b.h[nt], a.h, acc[nt], 0, 0, 0);
+            } else if constexpr (PREC == SGD_PREC_F16X3) {
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b.h[nt], a.l, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b.l[nt], a.h, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b.h[nt], a.h, acc[nt], 0, 0, 0);
@@ -156,14 +178,15 @@ template <int PREC, int NT> struct Frag {
 template <int PREC, int NCB> struct Frag16 {
     typedef typename Split<PREC>::T T;
     typedef T T8 __attribute__((ext_vector_type(8)));
-    static constexpr int NREADS = 2;              // ds_read_b128 per stage
-    static constexpr int NWLOADS = 2 * NCB;       // 16-byte global loads per K step
-    static constexpr int NMMA = 3 * NCB;          // MFMAs per stage
+    static constexpr bool ONE = prec_single(PREC);
+    static constexpr int NREADS = ONE ? 1 : 2;    // ds_read_b128 per stage
+    static constexpr int NWLOADS = (ONE ? 1 : 2) * NCB;  // 16-byte global loads per K step
+    static constexpr int NMMA = (ONE ? 1 : 3) * NCB;     // MFMAs per stage
     struct AU {
         T8 h, l;
         __device__ __forceinline__ void load(const float* rowp, int kg) {      // kg = lane >> 4: this lane's 8-channel group
             h = *reinterpret_cast<const T8*>(rowp + kg * 8);
-            l = *reinterpret_cast<const T8*>(rowp + kg * 8 + 4);
+            if constexpr (!ONE) l = *reinterpret_cast<const T8*>(rowp + kg * 8 + 4);
         }
     };
     struct B {
@@ -171,13 +194,17 @@ template <int PREC, int NCB> struct Frag16 {
         __device__ __forceinline__ void load(const char* p) {
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                h[cb] = *reinterpret_cast<const T8*>(p + (cb >> 1) * WUNIT + (cb & 1) * 256);
-                l[cb] = *reinterpret_cast<const T8*>(p + (cb >> 1) * WUNIT + (cb & 1) * 256 + 1024);
+                h[cb] = *reinterpret_cast<const T8*>(p + (cb >> 1) * wunit<PREC>() + (cb & 1) * 256);
+                if constexpr (!ONE) l[cb] = *reinterpret_cast<const T8*>(p + (cb >> 1) * WUNIT + (cb & 1) * 256 + 1024);
             }
         }
     };
     static __device__ __forceinline__ f32x4 mma1(f32x4 acc, const AU& a, const B& b) {      // column block 0 only
-        if constexpr (PREC == SGD_PREC_F16X3) {
+        if constexpr (PREC == SGD_PREC_F16) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[0], a.h, acc, 0, 0, 0);
+        } else if constexpr (PREC == SGD_PREC_BF16) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b.h[0], a.h, acc, 0, 0, 0);
+        } else if constexpr (PREC == SGD_PREC_F16X3) {
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[0], a.l, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.l[0], a.h, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[0], a.h, acc, 0, 0, 0);
@@ -191,7 +218,11 @@ template <int PREC, int NCB> struct Frag16 {
     static __device__ __forceinline__ void mma(f32x4 (&acc)[NCB], const AU& a, const B& b) {
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-            if constexpr (PREC == SGD_PREC_F16X3) {
+            if constexpr (PREC == SGD_PREC_F16) {
+                acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[cb], a.h, acc[cb], 0, 0, 0);
+            } else if constexpr (PREC == SGD_PREC_BF16) {
+                acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b.h[cb], a.h, acc[cb], 0, 0, 0);
+            } else if constexpr (PREC == SGD_PREC_F16X3) {
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[cb], a.l, acc[cb], 0, 0, 0);
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.l[cb], a.h, acc[cb], 0, 0, 0);
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.h[cb], a.h, acc[cb], 0, 0, 0);
@@ -1360,17 +1391,17 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
     }
     // weight fragments: wave (wm, wn) needs N blocks wn*NT .. wn*NT+NT-1 of its tile; consecutive K steps of the stream
     // [chunk][tap] are `wstep` bytes apart (all N blocks of the layer for that step)
-    const size_t wstep = (size_t)(a.cout_p >> 5) * WUNIT;
+    const size_t wstep = (size_t)(a.cout_p >> 5) * wunit<PREC>();
     // (the lane's offset inside a unit is re-derived per tile from the hardware lane index: as a 64-bit per-lane pointer held
     // from here on it was the kernel's last spilled value, and a kernel with any scratch pays ~3 us on every launch)
     auto wtile_of = [&](int k) __attribute__((always_inline)) {
         int l;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        const int loff = M16 ? (l >> 5) * 2048 + (((l >> 4) & 1) * 32 + (l & 15)) * 16 : l * 16;
+        const int loff = M16 ? (l >> 5) * wsub<PREC>() + (((l >> 4) & 1) * 32 + (l & 15)) * 16 : l * 16;
         const Tile T = tile_at<SUBPIX>(g, lin_of(k), BN, TW, TH);
-        // sub-pixel: the parity's own packed kernels, 4 taps x cin_p x cout_p x 4 bytes further per parity
-        const size_t pbase = SUBPIX ? (size_t)T.par * ((size_t)a.cin_p * a.cout_p * 16) : 0;
-        return reinterpret_cast<const char*>(a.w) + pbase + (size_t)(wn * NT + (T.n0c >> 5)) * WUNIT + loff;
+        // sub-pixel: the parity's own packed kernels, 4 taps x cin_p x cout_p x 4 (single-product modes: 2) bytes further per parity
+        const size_t pbase = SUBPIX ? (size_t)T.par * ((size_t)a.cin_p * a.cout_p * (wunit<PREC>() / 256)) : 0;
+        return reinterpret_cast<const char*>(a.w) + pbase + (size_t)(wn * NT + (T.n0c >> 5)) * wunit<PREC>() + loff;
     };
     // sub-pixel: LDS offset of the parity's first tap -- tap t = 2r + s of parity (a, b) reads halo (row + a + r, col + b + s)
     auto par_off = [&](int k) __attribute__((always_inline)) {
@@ -1434,7 +1465,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
                 constexpr int ntap = seam ? 0 : tap + 1;
                 if (!ABL(16)) acc[mt][cbi] = Frag16<PREC, 1>::mma1(acc[mt][cbi], ring[mt], fb16[cbi]);
                 if (cbi == CBN - 1 && !ABL(64)) ring[mt].load(nbase + tap_off(ntap) + aoff[mt], lane >> 4);
-                if (mt == RB - 1 && !ABL(32)) fb16[cbi].load(wnext + (cbi >> 1) * WUNIT + (cbi & 1) * 256);
+                if (mt == RB - 1 && !ABL(32)) fb16[cbi].load(wnext + (cbi >> 1) * wunit<PREC>() + (cbi & 1) * 256);
                 (void)pbase; (void)ptap; (void)pst; (void)wrap;
             } else {
                 if (!ABL(64)) ring[(st + DEPTH) % RING].load(pbase + tap_off(ptap) + aoff[pst % MT], pst / MT, lh);
@@ -1445,10 +1476,10 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
             // (a burst of reads in front of the MFMAs fills the LDS queue and the in-order wave cannot issue its MFMAs
             // until they are accepted)
             {
-                constexpr int NM = M16 ? 3 : FragT::NMMA;
-                constexpr int NR = M16 ? (st / RB == CBN - 1 ? 2 : 0) : FragT::NREADS;
+                constexpr int NM = M16 ? Frag16<PREC, 1>::NMMA : FragT::NMMA;
+                constexpr int NR = M16 ? (st / RB == CBN - 1 ? Frag16<PREC, 1>::NREADS : 0) : FragT::NREADS;
                 constexpr int P1 = NR < NM ? NR : NM;
-                constexpr int nw = M16 ? (st % RB == RB - 1 ? 2 : 0) : ((mt == MT - 1) ? FragT::NWLOADS : 0);
+                constexpr int nw = M16 ? (st % RB == RB - 1 ? Frag16<PREC, 1>::NWLOADS : 0) : ((mt == MT - 1) ? FragT::NWLOADS : 0);
                 constexpr int P2 = nw < NM - P1 ? nw : NM - P1;
 #pragma unroll
                 for (int i = 0; i < P1; ++i) {
@@ -1472,7 +1503,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
     const char* wp = wstart_of(0);                 // weight fragments of the CURRENT step
     if constexpr (M16) {
 #pragma unroll
-        for (int cb = 0; cb < CBN; ++cb) fb16[cb].load(wp + (cb >> 1) * WUNIT + (cb & 1) * 256);
+        for (int cb = 0; cb < CBN; ++cb) fb16[cb].load(wp + (cb >> 1) * wunit<PREC>() + (cb & 1) * 256);
     } else {
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) fb[ks].load(wp, ks);
@@ -1748,7 +1779,7 @@ int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
 }  // namespace
 
 #ifndef SGDM_IGEMM_PREC
-#error "igemm.hip is compiled once per arithmetic mode: -DSGDM_IGEMM_PREC=0|1|2 (build.py); geometry and entry points: igemm_host.hip"
+#error "igemm.hip is compiled once per arithmetic mode: -DSGDM_IGEMM_PREC=0..4 (build.py); geometry and entry points: igemm_host.hip"
 #endif
 #ifdef SGDM_DEV_ONE      /* development: compile ONE kernel instance (register / asm inspection), never linked */
 #define SGD_DISPATCH_BODY(P)                                                                                        \
@@ -1766,6 +1797,14 @@ int sgd_igemm_dispatch_f32(const void* kap, int bn, int vec, int taps, size_t sm
 int sgd_igemm_dispatch_f16x3_nopk(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_F16X3) }
 #elif SGDM_IGEMM_PREC == 1
 int sgd_igemm_dispatch_f16x3(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_F16X3) }
+#elif SGDM_IGEMM_PREC == 3 && defined(SGDM_IGEMM_NOPK)
+int sgd_igemm_dispatch_f16_nopk(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_F16) }
+#elif SGDM_IGEMM_PREC == 3
+int sgd_igemm_dispatch_f16(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_F16) }
+#elif SGDM_IGEMM_PREC == 4 && defined(SGDM_IGEMM_NOPK)
+int sgd_igemm_dispatch_bf16_nopk(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_BF16) }
+#elif SGDM_IGEMM_PREC == 4
+int sgd_igemm_dispatch_bf16(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_BF16) }
 #elif defined(SGDM_IGEMM_NOPK)
 int sgd_igemm_dispatch_bf16x3_nopk(const void* kap, int bn, int vec, int taps, size_t smem, hipStream_t st) { SGD_DISPATCH_BODY(SGD_PREC_BF16X3) }
 #else

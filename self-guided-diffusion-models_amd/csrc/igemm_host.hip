@@ -187,6 +187,10 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
     sgd_igemm_args& a = ka.a;
     Geo& g = ka.g;
     if (!a.x0 || !a.w || !a.y || a.c0 <= 0 || a.c1 < 0 || a.cout <= 0) return SGD_ERR_ARG;
+    // SGD_PREC_F16 / SGD_PREC_BF16 (single product, inference only) take every launch rule of the split modes below -- tile, MFMA
+    // form, sub-pixel, LayerNorm fence: all of them are written as `prec != SGD_PREC_F32`.  None has been re-measured for one product
+    // per term yet except where a comment says so.
+    if (a.prec < SGD_PREC_F32 || a.prec > SGD_PREC_BF16) return SGD_ERR_ARG;
     if (a.c1 > 0 && (!a.x1 || a.c0 % KC != 0)) return SGD_ERR_ARG;
     if (a.y_ld < a.cout) return SGD_ERR_ARG;
     if (a.pro != SGD_PRO_NONE && (!a.pa || !a.pb)) return SGD_ERR_ARG;
@@ -276,6 +280,10 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
                                             : sgd_igemm_dispatch_f16x3(&ka, bn, variant, taps, smem_launch, st);
         case SGD_PREC_BF16X3: return ln_nopk ? sgd_igemm_dispatch_bf16x3_nopk(&ka, bn, variant, taps, smem_launch, st)
                                              : sgd_igemm_dispatch_bf16x3(&ka, bn, variant, taps, smem_launch, st);
+        case SGD_PREC_F16: return ln_nopk ? sgd_igemm_dispatch_f16_nopk(&ka, bn, variant, taps, smem_launch, st)
+                                          : sgd_igemm_dispatch_f16(&ka, bn, variant, taps, smem_launch, st);
+        case SGD_PREC_BF16: return ln_nopk ? sgd_igemm_dispatch_bf16_nopk(&ka, bn, variant, taps, smem_launch, st)
+                                           : sgd_igemm_dispatch_bf16(&ka, bn, variant, taps, smem_launch, st);
         default: return SGD_ERR_ARG;
     }
 }

@@ -19,6 +19,7 @@ constexpr int A_THREADS = 256;  // 4 input-tile loader waves
 constexpr int NCOMP = 256;      // 4 compute (MFMA) waves, one per SIMD
 constexpr int NTHREADS = NCOMP + A_THREADS;
 constexpr int WUNIT = 4096;   // bytes of one packed weight unit: 32 output x 32 input channels of one tap, fragment order
+                              // (the single-product modes SGD_PREC_F16 / BF16 carry no lo half: WUNIT / 2, igemm.hip: wunit())
 constexpr int MIN_PART_STEPS = 27;   // K steps (tap x 32 channels) of the smallest K part worth splitting off
 constexpr int SPLIT_MAX = 4;   // K parts of a tile of the balanced tail (sgd_igemm_args.work)
 constexpr int WORK_TILES = 256;                        // split tiles of one launch: < blocks
@@ -95,12 +96,14 @@ inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace
 
-// One translation unit per arithmetic mode (build.py compiles igemm.hip with -DSGDM_IGEMM_PREC=0 / 1 / 2, in parallel: the kernel
+// One translation unit per arithmetic mode (build.py compiles igemm.hip with -DSGDM_IGEMM_PREC=0 .. 4, in parallel: the kernel
 // template has 12 instances per mode and eight epilogue variants each): the mode's launch dispatcher has external linkage, the
 // geometry and the entry points live in igemm_host.hip.  The argument block crosses as bytes.
 int sgd_igemm_dispatch_f32(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
 int sgd_igemm_dispatch_f16x3(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
 int sgd_igemm_dispatch_bf16x3(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
+int sgd_igemm_dispatch_f16(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);      // single product, inference
+int sgd_igemm_dispatch_bf16(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
 // The LayerNorm-row prologue (Attention_LR's to_q / to_kv, crossattetion_lr.py:81-88) in a split mode runs on instances compiled
 // with packed-f32 code generation OFF (build.py: -DSGDM_IGEMM_NOPK -Xclang -target-feature -Xclang -packed-fp32-ops; 1x1 / linear
 // instances only).  Round 4 found the two-plane instance of that prologue returning exactly beta -- the LayerNorm value with a zero
@@ -111,3 +114,7 @@ int sgd_igemm_dispatch_bf16x3(const void* ka, int bn, int vec, int taps, size_t 
 // spilled registers in the 3x3 instance); confined to these launches it costs C2 nothing and C4 / C5 the difference on ~20 launches.
 int sgd_igemm_dispatch_f16x3_nopk(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
 int sgd_igemm_dispatch_bf16x3_nopk(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
+// The single-product modes stage the same LayerNorm-row prologue through the same loader code (only the conversion behind it is
+// shorter), so their LayerNorm launches get the same fence: units of their own without packed-f32 instructions.
+int sgd_igemm_dispatch_f16_nopk(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);
+int sgd_igemm_dispatch_bf16_nopk(const void* ka, int bn, int vec, int taps, size_t smem, hipStream_t st);

@@ -13,6 +13,8 @@ namespace {
 //   unit(chunk, tap, nb) = 4 KiB holding the 32 output channels nb*32.. x 32 input channels chunk*32.. of one tap,
 //   units ordered [chunk][tap][nb] (nb over ALL cout_p / 32 blocks: a K step of the stream is contiguous).
 //   split modes: unit = [ks 0..1][hi | lo][lane 0..63][8 x 16-bit]   lane = lh*32 + li holds W[nb*32+li][chunk*32+ks*16+lh*8 .. +7]
+//   single-product modes (SGD_PREC_F16 / BF16): the split unit without its lo halves, 2 KiB: [ks 0..1][lane 0..63][8 x 16-bit],
+//                the operand rounded once (the hi half of the split of the same scaled value)
 //   f32        : unit = [ks 0..3][lane 0..63][4 x f32]               lane = lh*32 + li holds W[nb*32+li][chunk*32+ks*8+lh*4 .. +3]
 //   (exactly the A-operand lane map of v_mfma_f32_32x32x16_f16 / four v_mfma_f32_32x32x2_f32 k-pairs).
 // One thread produces one lane's 16 bytes (f32) or its hi AND lo 16 bytes (split) of one sub-step.
@@ -114,9 +116,13 @@ __device__ __forceinline__ void pack_weight_body(const float* __restrict__ src, 
                 h[j] = hj;
                 l[j] = lj;
             }
-            T* up = reinterpret_cast<T*>(dst + unit * 1024) + sub * 1024 + lane * 8;
-            *reinterpret_cast<T8*>(up) = h;
-            *reinterpret_cast<T8*>(up + 512) = l;
+            if constexpr (prec_single(PREC)) {
+                *reinterpret_cast<T8*>(reinterpret_cast<T*>(dst) + unit * 1024 + sub * 512 + lane * 8) = h;
+            } else {
+                T* up = reinterpret_cast<T*>(dst + unit * 1024) + sub * 1024 + lane * 8;
+                *reinterpret_cast<T8*>(up) = h;
+                *reinterpret_cast<T8*>(up + 512) = l;
+            }
         }
     }
 }
@@ -205,9 +211,13 @@ __device__ __forceinline__ void pack_subpixel_body(const float* __restrict__ src
             h[j] = hj;
             l[j] = lj;
         }
-        T* up = reinterpret_cast<T*>(dst + unit * 1024) + sub * 1024 + lane * 8;
-        *reinterpret_cast<T8*>(up) = h;
-        *reinterpret_cast<T8*>(up + 512) = l;
+        if constexpr (prec_single(PREC)) {
+            *reinterpret_cast<T8*>(reinterpret_cast<T*>(dst) + unit * 1024 + sub * 512 + lane * 8) = h;
+        } else {
+            T* up = reinterpret_cast<T*>(dst + unit * 1024) + sub * 1024 + lane * 8;
+            *reinterpret_cast<T8*>(up) = h;
+            *reinterpret_cast<T8*>(up + 512) = l;
+        }
     }
 }
 template <int PREC>
@@ -260,11 +270,11 @@ __global__ void pack_weight_batched_kernel(const sgd_pack_job* __restrict__ jobs
 static inline int pick_bn(int cout) { return (cout % 128 == 0) ? 128 : 32; }
 
 extern "C" int64_t sgd_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ksize, int32_t prec) {
-    (void)prec;
     const int bn = pick_bn(cout);
     const int64_t cout_p = (int64_t)((cout + bn - 1) / bn) * bn;
     const int64_t cin_p = (int64_t)((cin + KC - 1) / KC) * KC;
-    return (int64_t)ksize * ksize * cout_p * cin_p * 4;
+    // 4 bytes per weight (f32, or hi + lo), 2 in the single-product modes (no lo half)
+    return (int64_t)ksize * ksize * cout_p * cin_p * (prec == SGD_PREC_F16 || prec == SGD_PREC_BF16 ? 2 : 4);
 }
 
 static int pack_weight_impl(const float* w_src, void* w_dst, int32_t cout, int32_t cin, int32_t ksize, int32_t prec,
@@ -285,6 +295,8 @@ static int pack_weight_impl(const float* w_src, void* w_dst, int32_t cout, int32
     if (prec == SGD_PREC_F32) hipLaunchKernelGGL((pack_weight_kernel<SGD_PREC_F32>), dim3(grid), dim3(256), 0, st, w_src, dst, cout, cin, ksize, cout_p, cin_p, transpose, amax_bits, scale_inv_out);
     else if (prec == SGD_PREC_F16X3) hipLaunchKernelGGL((pack_weight_kernel<SGD_PREC_F16X3>), dim3(grid), dim3(256), 0, st, w_src, dst, cout, cin, ksize, cout_p, cin_p, transpose, amax_bits, scale_inv_out);
     else if (prec == SGD_PREC_BF16X3) hipLaunchKernelGGL((pack_weight_kernel<SGD_PREC_BF16X3>), dim3(grid), dim3(256), 0, st, w_src, dst, cout, cin, ksize, cout_p, cin_p, transpose, amax_bits, scale_inv_out);
+    else if (prec == SGD_PREC_F16) hipLaunchKernelGGL((pack_weight_kernel<SGD_PREC_F16>), dim3(grid), dim3(256), 0, st, w_src, dst, cout, cin, ksize, cout_p, cin_p, transpose, amax_bits, scale_inv_out);
+    else if (prec == SGD_PREC_BF16) hipLaunchKernelGGL((pack_weight_kernel<SGD_PREC_BF16>), dim3(grid), dim3(256), 0, st, w_src, dst, cout, cin, ksize, cout_p, cin_p, transpose, amax_bits, scale_inv_out);
     else return SGD_ERR_ARG;
     return sgd_check_launch();
 }
@@ -356,13 +368,15 @@ extern "C" int sgd_pack_weight_subpixel_scaled(const float* w_src, void* w_dst, 
     float* dst = reinterpret_cast<float*>(w_dst);
     if (prec == SGD_PREC_F16X3) hipLaunchKernelGGL((pack_subpixel_kernel<SGD_PREC_F16X3>), grid, dim3(256), 0, st, w_src, dst, cout, cin, cout_p, cin_p, amax_bits, scale_inv_out);
     else if (prec == SGD_PREC_BF16X3) hipLaunchKernelGGL((pack_subpixel_kernel<SGD_PREC_BF16X3>), grid, dim3(256), 0, st, w_src, dst, cout, cin, cout_p, cin_p, amax_bits, scale_inv_out);
+    else if (prec == SGD_PREC_F16) hipLaunchKernelGGL((pack_subpixel_kernel<SGD_PREC_F16>), grid, dim3(256), 0, st, w_src, dst, cout, cin, cout_p, cin_p, amax_bits, scale_inv_out);
+    else if (prec == SGD_PREC_BF16) hipLaunchKernelGGL((pack_subpixel_kernel<SGD_PREC_BF16>), grid, dim3(256), 0, st, w_src, dst, cout, cin, cout_p, cin_p, amax_bits, scale_inv_out);
     else return SGD_ERR_ARG;
     return sgd_check_launch();
 }
 
 extern "C" int sgd_pack_job_blocks(int32_t cout, int32_t cin, int32_t ksize, int32_t prec, int32_t transpose, int32_t* amax_blocks,
                                    int32_t* pack_blocks, int32_t* cin_p_out, int32_t* cout_p_out) {
-    if (cout <= 0 || cin <= 0 || (ksize != 1 && ksize != 3)) return SGD_ERR_ARG;
+    if (cout <= 0 || cin <= 0 || (ksize != 1 && ksize != 3) || prec < SGD_PREC_F32 || prec > SGD_PREC_BF16) return SGD_ERR_ARG;
     if (transpose < SGD_PACK_FORWARD || transpose > SGD_PACK_SUBPIXEL) return SGD_ERR_ARG;
     if (transpose == SGD_PACK_SUBPIXEL && (ksize != 3 || prec == SGD_PREC_F32)) return SGD_ERR_ARG;
     const int co = transpose == SGD_PACK_DGRAD ? cin : cout, ci = transpose == SGD_PACK_DGRAD ? cout : cin;
@@ -388,6 +402,7 @@ extern "C" int sgd_pack_weights_batched(const sgd_pack_job* jobs, int32_t n_jobs
     SGD_CLEAR_ERR();
     if (!jobs || n_jobs <= 0 || !pack_block_job || !pack_first || n_pack_blocks <= 0) return SGD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
+    if (prec < SGD_PREC_F32 || prec > SGD_PREC_BF16) return SGD_ERR_ARG;     // before the amax launches: nothing runs for an unknown mode
     if (prec != SGD_PREC_F32 && n_amax_blocks > 0) {
         if (!amax_block_job || !amax_first) return SGD_ERR_ARG;
         hipLaunchKernelGGL(pack_zero_amax_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, st, jobs, n_jobs);
@@ -396,6 +411,8 @@ extern "C" int sgd_pack_weights_batched(const sgd_pack_job* jobs, int32_t n_jobs
     if (prec == SGD_PREC_F32) hipLaunchKernelGGL((pack_weight_batched_kernel<SGD_PREC_F32>), dim3(n_pack_blocks), dim3(256), 0, st, jobs, pack_block_job, pack_first);
     else if (prec == SGD_PREC_F16X3) hipLaunchKernelGGL((pack_weight_batched_kernel<SGD_PREC_F16X3>), dim3(n_pack_blocks), dim3(256), 0, st, jobs, pack_block_job, pack_first);
     else if (prec == SGD_PREC_BF16X3) hipLaunchKernelGGL((pack_weight_batched_kernel<SGD_PREC_BF16X3>), dim3(n_pack_blocks), dim3(256), 0, st, jobs, pack_block_job, pack_first);
+    else if (prec == SGD_PREC_F16) hipLaunchKernelGGL((pack_weight_batched_kernel<SGD_PREC_F16>), dim3(n_pack_blocks), dim3(256), 0, st, jobs, pack_block_job, pack_first);
+    else if (prec == SGD_PREC_BF16) hipLaunchKernelGGL((pack_weight_batched_kernel<SGD_PREC_BF16>), dim3(n_pack_blocks), dim3(256), 0, st, jobs, pack_block_job, pack_first);
     else return SGD_ERR_ARG;
     return sgd_check_launch();
 }

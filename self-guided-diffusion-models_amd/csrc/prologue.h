@@ -30,6 +30,25 @@ template <> struct Split<SGD_PREC_BF16X3> {
     }
 };
 
+// Single-product inference modes (SGD_PREC_F16 / SGD_PREC_BF16): the operand is rounded ONCE (round to nearest even; the bf16 cast is
+// the plain one, so a NaN stays a NaN) and there is no lo half -- hi() is all the kernels use; split() exists so that shared code
+// compiles and returns a zero lo.
+template <> struct Split<SGD_PREC_F16> {
+    typedef _Float16 T;
+    static __device__ __forceinline__ T hi(float v) { return (T)v; }
+    static __device__ __forceinline__ float back(T h) { return (float)h; }
+    static __device__ __forceinline__ void split(float v, T& h, T& l) { h = (T)v; l = (T)0.f; }
+};
+template <> struct Split<SGD_PREC_BF16> {
+    typedef __bf16 T;
+    static __device__ __forceinline__ T hi(float v) { return (T)v; }
+    static __device__ __forceinline__ float back(T h) { return (float)h; }
+    static __device__ __forceinline__ void split(float v, T& h, T& l) { h = (T)v; l = (T)0.f; }
+};
+// single-product mode (no lo half anywhere: LDS rows, packed weights, MFMAs) / f16 element type
+constexpr bool prec_single(int prec) { return prec == SGD_PREC_F16 || prec == SGD_PREC_BF16; }
+constexpr bool prec_f16(int prec) { return prec == SGD_PREC_F16X3 || prec == SGD_PREC_F16; }
+
 // Four fp32 values -> packed f16 hi pairs and lo pairs in 8 vector instructions: v_cvt_pk_f16_f32 (RNE, two values per
 // instruction) for hi, v_fma_mix_f32 for lo_f32 = v - float(hi) reading the f16 half directly (no v_cvt_f32_f16), and
 // v_cvt_pk_f16_f32 again for lo.  The compiler's own sequence for the same arithmetic is 16 instructions (it converts hi
@@ -51,6 +70,20 @@ __device__ __forceinline__ void split4_f16(f32x4 v, u32x2& h, u32x2& l) {
     h.x = h.y = l.x = l.y = 0;
     (void)v;
 #endif
+}
+
+// the hi half alone (SGD_PREC_F16): the same two v_cvt_pk_f16_f32 as split4_f16, so the rounded operand is bit for bit f16x3's hi
+__device__ __forceinline__ u32x2 round4_f16(f32x4 v) {
+    u32x2 h;
+#if defined(__HIP_DEVICE_COMPILE__)
+    float v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3];
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h.x) : "v"(v0), "v"(v1));
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h.y) : "v"(v2), "v"(v3));
+#else
+    h.x = h.y = 0;
+    (void)v;
+#endif
+    return h;
 }
 
 // raw input vector: 4 consecutive channels starting at c of source row `row` (virtual concat x0|x1)

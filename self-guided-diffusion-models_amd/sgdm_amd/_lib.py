@@ -18,9 +18,11 @@ LIB_PATH = os.environ.get("SGDM_LIB_PATH") or os.path.join(_HERE, "lib", "libsgd
 MODE_FLAT, MODE_CONV3 = 0, 1
 RS_NONE, RS_AVGPOOL2, RS_UP2, RS_ZEROUP2, RS_UP2_SUBPIXEL = 0, 1, 2, 3, 4
 PRO_NONE, PRO_AFFINE_NC, PRO_LN_ROW = 0, 1, 2
-PREC_F32, PREC_F16X3, PREC_BF16X3 = 0, 1, 2
-PREC_BY_NAME = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3}
-ABI_VERSION = 23
+PREC_F32, PREC_F16X3, PREC_BF16X3, PREC_F16, PREC_BF16 = 0, 1, 2, 3, 4
+PREC_BY_NAME = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "bf16": PREC_BF16}
+# single-product modes (operands rounded once to 16 bits, one MFMA product per term): inference only -- train.py refuses them
+INFERENCE_ONLY = ("f16", "bf16")
+ABI_VERSION = 24
 
 # sgd_igemm_args.tune (include/sgdm_hip.h: SGD_TUNE_*): per-call schedule overrides for parity tests and A/B tools
 TUNE_BN128, TUNE_BN256, TUNE_FLAT2, TUNE_DEFER, TUNE_PLAIN_SCHEDULE, TUNE_LN_PACKED, TUNE_NO_SMALL = 1, 2, 4, 8, 16, 32, 64

@@ -108,6 +108,9 @@ class CrossAttention(nn.Module):
             raise RuntimeError("sgdm_amd attention_ldm modules run on the MI355X HIP path only; there is no CPU fallback")
         if torch.is_grad_enabled() and (x.requires_grad or context.requires_grad
                                         or any(p.requires_grad for p in self.parameters())):
+            if self.hip_precision in L.INFERENCE_ONLY:
+                raise ValueError(f"hip_precision='{self.hip_precision}' is inference only: run under torch.no_grad(), or train "
+                                 f"with 'f32', 'f16x3' or 'bf16x3'")
             return _CrossAttnFn.apply(self, mask, x, context, *self.parameters())
         return self._run(x, context, mask, None)
 
@@ -165,7 +168,7 @@ class CrossAttention(nn.Module):
             L.check(lib.sgd_attention_masked(_ptr(q), inner, dp, kp, vp, 2 * inner, dp, _ptr(kmask), b, heads, n, J, dp,
                                              self.scale, _ptr(att), inner, lp, st), "sgd_attention_masked")
         else:
-            fn = lib.sgd_attention_split if prec == L.PREC_F16X3 else lib.sgd_attention
+            fn = lib.sgd_attention_split if prec in (L.PREC_F16X3, L.PREC_F16) else lib.sgd_attention
             L.check(fn(_ptr(q), inner, dp, kp, vp, 2 * inner, dp, b, heads, n, J, dp, self.scale, _ptr(att), inner, lp, st),
                     "sgd_attention")
         o = torch.empty(b, n, dim, device=dev)

@@ -123,6 +123,8 @@ class Backward:
         each bucket's all-reduce is enqueued on a side stream as soon as the launches filling it are issued."""
         self.e, self.lib, self.n, self.dev, self.prec = eng, eng.lib, eng.n, eng.dev, eng.prec
         self.m = eng.m
+        if self.prec in (L.PREC_F16, L.PREC_BF16):
+            raise ValueError("hip_precision 'f16' / 'bf16' is inference only: no backward program exists for a single-product engine")
         self.prog = _Program()
         self.packs, self.late, self.late_at = [], [], []
         self.arena, self.reducer = arena, reducer
@@ -956,8 +958,20 @@ def make_backward(eng):
     return Backward(eng, arena, BucketReducer(arena, group=exchange_group(), average=False, force=exchange_forced(eng.m)))
 
 
+def refuse_inference_only(model):
+    """the single-product modes (hip_precision 'f16' / 'bf16') have no backward: half-precision training needs loss-scale and
+    master-weight decisions this library has not made.  Raises before anything is launched."""
+    mods = model.modules() if isinstance(model, torch.nn.Module) else ()
+    for mod in mods:
+        name = getattr(mod, "hip_precision", None)
+        if name in L.INFERENCE_ONLY:
+            raise ValueError(f"hip_precision='{name}' is inference only (operands rounded once to 16 bits, no backward): "
+                             f"train with 'f32', 'f16x3' or 'bf16x3', or run this model under torch.no_grad() / eval()")
+
+
 def forward_train(model, x, t, cond, layout, mask, n):
     """autograd-capable UNet evaluation (called from UNetModelBase._run when grads are required)"""
+    refuse_inference_only(model)
     B, cx, H, W = x.shape
     if getattr(model, "use_spatial_transformer", False):
         # the reference cannot train this variant either: BasicTransformerBlock checkpoints _forward(x, context) with
@@ -1005,6 +1019,9 @@ class _MSEFn(torch.autograd.Function):
 
 def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     """LatentDiffusion.p_losses (ddpm.py:54-86)"""
+    fn = getattr(diff.denoise_fn, "__self__", diff.denoise_fn)        # the UNet (a bound forward or the module itself)
+    if torch.is_grad_enabled() and isinstance(fn, torch.nn.Module) and fn.training and any(p.requires_grad for p in fn.parameters()):
+        refuse_inference_only(fn)                                         # a training step: before the first launch
     lib = L.load()
     h = diff.hparams
     noise = torch.randn_like(x_start) if noise is None else noise

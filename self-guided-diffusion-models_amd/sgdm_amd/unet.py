@@ -370,7 +370,8 @@ class UNetModelBase(nn.Module):
             # (the reference's own forward raises with the flag set -- `h = x.type(torch.float16)` meets fp32 weights,
             # openaimodel.py:564,926: "Input type (c10::Half) and bias type (float) should be the same" -- unless a caller has run
             # convert_to_fp16() (:837), and nothing in the reference calls it)
-            raise NotImplementedError("use_fp16=True is not supported (reference configs use fp32)")
+            raise NotImplementedError("use_fp16=True is not supported (reference configs use fp32); for half-precision "
+                                      "inference set hip_precision='f16' (or 'bf16') on the model, or SGDM_PREC=f16")
         if num_heads == -1 and num_head_channels == -1:
             raise AssertionError("Either num_heads or num_head_channels has to be set")
         if not conv_resample:
@@ -614,8 +615,9 @@ class _Engine:
 
     def attention_fn(self):
         """the attention core in the engine's arithmetic: split-precision MFMA for f16x3, exact fp32 otherwise
-        (bf16x3 keeps the exact kernel: 8 mantissa bits per half do not hold the softmax weights)"""
-        return self.lib.sgd_attention_split if self.prec == L.PREC_F16X3 else self.lib.sgd_attention
+        (bf16x3 keeps the exact kernel: 8 mantissa bits per half do not hold the softmax weights).  The single-product
+        modes take their x3 sibling's core (f16 -> split, bf16 -> exact): the cores are a small share of the step"""
+        return self.lib.sgd_attention_split if self.prec in (L.PREC_F16X3, L.PREC_F16) else self.lib.sgd_attention
 
     def pack(self, names, ksize, pad=None, subpixel=False):
         pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad, subpixel)

@@ -5,7 +5,7 @@ sgd_igemm_args (the library reads no environment), anything else is put into the
 ABI 15; rounds are interleaved, median and min reported, outputs of all variants compared with the first.
 
     python tools/ab_conv.py --variants base=lib/libsgdm_hip_base.so new=lib/libsgdm_hip.so new256=lib/libsgdm_hip.so:tune=2 \
-        --shapes 80,256,256,64 80,512,512,32 ... [--rounds 7] [--reps 20] [--prec f16x3] [--plain]
+        --shapes 80,256,256,64 80,512,512,32 ... [--rounds 7] [--reps 20] [--prec f32|f16x3|bf16x3|f16|bf16] [--plain]
 shape = n,cin,cout,hw[,ks[,up]]: up = 1 -- the nearest-x2-upsample conv of a hw x hw input (ResBlock up / Upsample, no
 residual); a variant with `subpixel=1` runs it as the sub-pixel conv (SGD_RS_UP2_SUBPIXEL) on the sub-pixel pack:
     --variants direct=lib/libsgdm_hip.so sub128=lib/libsgdm_hip.so:subpixel=1:tune=1 sub256=lib/libsgdm_hip.so:subpixel=1:tune=2 \

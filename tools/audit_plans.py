@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One forward evaluation and one training step of every shipped config/dynamic/*.yaml plan at its full width on the HIP path,
 each against the oracle (forward eps; loss and every parameter gradient): which plans run, and how close.
-    python tools/audit_plans.py [--prec f16x3] [--plans unet,unetca,...]  > profiles/r6_audit_plans.txt      (MI355X)
+    python tools/audit_plans.py [--prec f16x3|bf16x3|f32|f16|bf16] [--plans unet,unetca,...]  > profiles/r6_audit_plans.txt      (MI355X)
 The plans (reference config/dynamic/): unet_fast, unet_fast_s64, unetca_fast, unetca_fast_s64 come from tests/golden/unet_index.json
 (ctor kwargs recorded from the yaml files); unet (attention at ds 2 and 4 with 32 heads: 8 and 16 channels per head) and unetca
 (attention at ds 4 and 2) are those entries with the yaml's differences applied."""
@@ -119,6 +119,11 @@ def main():
                         layout=lay.cuda() if lay is not None else None, cond_drop_prob=0.0)[0]
                 ref = U.unet_forward(cfg, w, batch["image"], t, cnd, lay, None)
             ferr = max_rel(eps.cpu(), ref)
+            from sgdm_amd import _lib as L
+            if a.prec in L.INFERENCE_ONLY:                                # 'f16' / 'bf16': no train step to audit
+                smp = ("  samplers: " + sample_audit(m, kw, e, batch, B, S)) if a.sample else ""
+                print(f"{name:16s} OK  forward {ferr:.2e} | inference-only mode: no train step{smp}  [{time.time() - t0:.0f} s]", flush=True)
+                continue
             m.train()
             d = LatentDiffusion(device="cuda", **bench.MODEL_PARAMS).train()
             d.set_denoise_fn(m.forward, m.forward_with_cond_scale)

@@ -22,7 +22,7 @@ import bench  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3", "bf16x3"])
+    ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3", "bf16x3", "f16", "bf16"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--native-reps", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pndm_vs_ddim_c2.txt"))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch table of one UNet evaluation (HIP events around every launch).
-    python tools/profile_layers.py [--workload c2] [--prec f16x3] [--batch 40] [--no-subpixel]
+    python tools/profile_layers.py [--workload c2] [--prec f32|f16x3|bf16x3|f16|bf16] [--batch 40] [--no-subpixel]
 --no-subpixel: the nearest-upsample 3x3 convs as direct SGD_RS_UP2 launches (SGDM_SUBPIXEL=0) instead of sub-pixel ones"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
