@@ -393,6 +393,22 @@ typedef struct sgd_pndm_row {
 } sgd_pndm_row;
 int sgd_pndm_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, float w, const sgd_pndm_row* row_dev,
                   float* acc, float* base, float* ring, int32_t b, int32_t c, int32_t hw, float* x_out, void* stream);
+/* DPM-Solver++(2M) update (Lu et al. 2022, Algorithm 2: second-order multistep on the DATA prediction; no counterpart in the
+ * reference): ONE launch per UNet evaluation.  The step's scalars are read from a row in DEVICE memory and the previous
+ * data prediction from `x0_hist` [b*c*hw], so one captured step replays for every step of a trajectory
+ * (sgdm_amd/diffusion.py: DPMSolverSampler).  Per element, with e the guided eps, each product rounded before it is added:
+ *   x0    = (x - s1ma * e) * rsa;   clip != 0: x0 = min(max(x0, -1), 1)
+ *   D     = cp != 0 ? cc * x0 + cp * x0_hist : cc * x0      (x0_hist is NOT read when cp == 0: it may be uninitialised)
+ *   x_out = A * x + B * D;          x0_hist = x0            (the history is also the step's x0 output)
+ * s1ma = sqrt(1 - at), rsa = 1 / sqrt(at), A = sqrt((1 - ap) / (1 - at)), B = sqrt(ap) - A sqrt(at); with h = lam(ap) - lam(at),
+ * lam(v) = log(v / (1 - v)) / 2 and r = h_prev / h: cc = 1 + 1 / (2r), cp = -1 / (2r); first-order rows have cc = 1, cp = 0.
+ * All formed by the caller in double and rounded once.  eps_nhwc as for the step kernels above (cfg_mode 0: b*c one-channel
+ * planes).  x_out == x allowed; x0_hist must not alias x or x_out. */
+typedef struct sgd_dpmpp_row {
+    float s1ma, rsa, A, B, cc, cp, pad0, pad1;
+} sgd_dpmpp_row;
+int sgd_dpmpp_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, float w, const sgd_dpmpp_row* row_dev,
+                   float* x0_hist, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out, void* stream);
 /* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s

@@ -31,6 +31,8 @@ FILE_FLAGS = {"igemm.hip": ["-fno-slp-vectorize"], "pack.hip": ["-fno-slp-vector
 # pndm.hip: no contraction -- the PNDM update is the reference's torch op sequence, rounding for rounding (a later
 # -ffp-contract=off overrides the global =fast; `#pragma clang fp contract(off)` does not)
 FILE_FLAGS["pndm.hip"] = ["-ffp-contract=off"]
+# dpm.hip: the same -- the DPM-Solver++ update is bit-equal to its torch-fp32 restatement only product by product
+FILE_FLAGS["dpm.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

@@ -144,6 +144,7 @@ SIGNATURES = {
     "sgd_to_uint8": (i32, [vp, i64, vp, vp]),
     "sgd_cfg_combine": (i32, [vp, i32, f32, i32, i32, i32, vp, vp]),
     "sgd_pndm_step": (i32, [vp, vp, i32, f32, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "sgd_dpmpp_step": (i32, [vp, vp, i32, f32, vp, vp, i32, i32, i32, i32, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

@@ -6,6 +6,7 @@ Mirrors (reference, /root/reference):
     diffusion/sampler/ddim_plms_sampler.py:25-391 DDIMSampler     ('ddim', 'plms')
     diffusion/sampler/pndm_sampler.py:13-211      PNDM_Sampler    ('pndm', include/sgdm_hip.h: sgd_pndm_step)
     dynamic/diffusionmodules/util.py:23-74        schedules / DDIM tables (deterministic host math)
+Without a counterpart there: DPMSolverSampler ('dpmsolver', DPM-Solver++(2M), include/sgdm_hip.h: sgd_dpmpp_step).
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -280,6 +281,20 @@ class _GraphedPNDMStep(_GraphedStep):
                                        _ptr(self.base), _ptr(self.ring), B, Cc, hw, _ptr(img), st), "sgd_pndm_step")
 
 
+class _GraphedDPMStep(_GraphedStep):
+    """The captured step of the DPM-Solver++(2M) sampler: UNet at 2B + ``sgd_dpmpp_step``.  ``coef`` holds one
+    ``sgd_dpmpp_row`` (include/sgdm_hip.h); ``x0``, the clipped data prediction the snapshots log, is also the multistep
+    history the next replay reads.  A trajectory's first row has ``cp == 0``, so what an earlier trajectory left in the
+    cached graph's ``x0`` is never read.  No ``z`` is drawn."""
+
+    COEF = (8, torch.float32)
+    NOISE = False
+
+    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
+        L.check(self.lib.sgd_dpmpp_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.coef), _ptr(self.x0), clip,
+                                        B, Cc, hw, _ptr(img), st), "sgd_dpmpp_step")
+
+
 def _quantile_rank(dtp, count):
     """(lo, hi, frac) of torch.quantile(., dtp) over `count` fp32 values: rank = q * (count - 1) in the input dtype,
     linear interpolation between the order statistics floor(rank) and ceil(rank)"""
@@ -362,6 +377,26 @@ class _EagerPNDMStep:
                                               _ptr(self.base), _ptr(self.ring), bb, cc, self.hw, _ptr(nxt), _stream()),
                 "sgd_pndm_step")
         self.img = nxt
+
+    def final(self):
+        return self.img
+
+
+class _EagerDPMStep:
+    """``_GraphedDPMStep`` launched kernel by kernel (generic ``denoise_sample_fn``, the ``cond_scale`` 0 / 1 shortcuts,
+    ``p0``, ``hip_graph=False``); the image ping-pongs between two buffers"""
+
+    def __init__(self, runner, img, clip, times, tab):
+        self.runner, self.img, self.clip = runner, img, clip
+        self.hw = int(np.prod(img.shape[2:]))
+        self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
+        self.nxt, self.x0 = torch.empty_like(img), torch.empty_like(img)
+
+    def step(self, i):
+        eps, mode, w, bb, cc = self.runner.eps(self.img, self.ts[i])
+        L.check(self.runner.lib.sgd_dpmpp_step(_ptr(self.img), _ptr(eps), mode, w, _ptr(self.tab[i]), _ptr(self.x0),
+                                               self.clip, bb, cc, self.hw, _ptr(self.nxt), _stream()), "sgd_dpmpp_step")
+        self.img, self.nxt = self.nxt, self.img
 
     def final(self):
         return self.img
@@ -763,6 +798,99 @@ class PNDM_Sampler(object):
         return img, dict(pred_x0=img)
 
 
+class DPMSolverSampler(object):
+    """DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2): second-order multistep on the DATA prediction, one UNet evaluation
+    per step, no warm-up, deterministic.  Not in the reference.  Per step ONE UNet call (at 2B on the fused-CFG path) and
+    ONE ``sgd_dpmpp_step`` launch whose scalars are a row of the trajectory's table (``plan``).
+
+    Sampling kwargs read: ``num_timesteps`` (S), ``alphas_cumprod``, ``clip_denoised``, ``log_num_per_prog``, and for direct
+    callers ``dpm_spacing`` ('logsnr' | 'uniform' | 'quad', default 'logsnr'), ``dpm_order`` (1 | 2, default 2) and
+    ``dpm_lower_order_final`` (default: fewer than 15 times).  ``ddim_eta``, ``temperature``, ``noise_dropout`` and ``vis`` are
+    ignored; ``dtp < 1`` is refused.  eps parameterization only, like 'ddim'.  Tests may inject ``x_T=``."""
+
+    def __init__(self, ddpm_num_timesteps, device):
+        self.ddpm_num_timesteps = ddpm_num_timesteps
+        self.device = device
+
+    def time_steps(self, sampling_kwargs, lam):
+        """ascending table indices; ``lam``: float64 half-log-SNR of every table entry"""
+        S, T = int(sampling_kwargs["num_timesteps"]), self.ddpm_num_timesteps
+        kind = sampling_kwargs.get("dpm_spacing", "logsnr")
+        if S < 1:
+            raise ValueError(f"dpmsolver: num_timesteps={S}")
+        if kind == "uniform":
+            if S > T:
+                raise ValueError(f"dpmsolver: num_timesteps={S} > {T}")
+            ts = make_ddim_timesteps("uniform", S, T)
+        elif kind == "quad":
+            ts = np.unique(make_ddim_timesteps("quad", S, T))
+        elif kind == "logsnr":
+            # uniform in log-SNR between the two ends of the table (DPM-Solver's recommendation for small images), each
+            # target mapped to the nearest table entry
+            targets = np.linspace(lam[T - 1], lam[1], S)
+            ts = np.unique([1 + int(np.abs(lam[1:T] - v).argmin()) for v in targets])
+        else:
+            raise ValueError(f"dpmsolver: unknown dpm_spacing '{kind}' (logsnr, uniform, quad)")
+        ts = np.asarray(ts, dtype=np.int64)
+        if len(ts) < 2:
+            raise ValueError(f"dpmsolver: num_timesteps={S} with dpm_spacing='{kind}' leaves {len(ts)} distinct time(s); 2 needed")
+        if ts[-1] >= T:
+            raise ValueError(f"dpmsolver: num_timesteps={S} with dpm_spacing='{kind}' reaches table index {int(ts[-1])} >= {T}")
+        return ts
+
+    def plan(self, sampling_kwargs):
+        """(ts, [len(ts), 8] fp32 table of sgd_dpmpp_row): row i is the step from table index ts[i] to ts[i-1] (to 0 for
+        i = 0); the trajectory visits the rows from the last to the first.  float64 math from the fp32 ``alphas_cumprod``,
+        rounded once."""
+        sk = sampling_kwargs
+        order = sk.get("dpm_order", 2)
+        if order not in (1, 2):
+            raise ValueError(f"dpmsolver: dpm_order={order!r} (1 or 2)")
+        a = sk["alphas_cumprod"].detach().float().cpu().double().numpy()
+        assert a.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
+        lam = 0.5 * np.log(a / (1.0 - a))
+        ts = self.time_steps(sk, lam)
+        n = len(ts)
+        lof = sk.get("dpm_lower_order_final")
+        lof = n < 15 if lof is None else bool(lof)
+        at, ap = a[ts], np.concatenate([a[:1], a[ts[:-1]]])
+        A = np.sqrt((1.0 - ap) / (1.0 - at))
+        B = np.sqrt(ap) - A * np.sqrt(at)                   # alpha_prev (1 - exp(-h)) without logarithms
+        h = 0.5 * np.log(ap / (1.0 - ap)) - 0.5 * np.log(at / (1.0 - at))
+        cc, cp = np.ones(n), np.zeros(n)
+        if order == 2:
+            r = h[1:] / h[:-1]                              # row i follows row i + 1: r = h_prev / h
+            cc[:-1], cp[:-1] = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+            if lof:
+                cc[0], cp[0] = 1.0, 0.0
+        tab = np.stack([np.sqrt(1.0 - at), 1.0 / np.sqrt(at), A, B, cc, cp, np.zeros(n), np.zeros(n)], 1)
+        return ts, torch.tensor(tab, dtype=torch.float64).float()
+
+    @torch.no_grad()
+    def sample(self, shape, sampling_kwargs, denoise_sample_fn=None, denoise_sample_fn_kwargs=None, **kwargs):
+        sk = sampling_kwargs
+        if sk.get("dtp", 1) < 1.0:
+            raise ValueError("dpmsolver: dynamic thresholding (dtp < 1) is not implemented for this sampler")
+        ts, tab = self.plan(sk)
+        dev = torch.device(self.device)
+        # a private copy: the trajectory is updated in place in the captured step
+        img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        clip = 1 if sk["clip_denoised"] else 0
+        total = len(ts)
+        snaps = _Snapshots(total, sk)
+        # noise dropout is ignored (no noise is drawn): only the model / guidance conditions of the captured step apply
+        if _graph_ok(runner, dict(sk, noise_dropout=0)):
+            stepper = _GraphedDPMStep.get(runner, img, "dpmsolver", clip, ts, tab)
+        else:
+            stepper = _EagerDPMStep(runner, img, clip, ts, tab)
+        for index in reversed(range(total)):
+            stepper.step(index)
+            if index in snaps.rows:
+                snaps.take(stepper)
+        return snaps.result(stepper, shape)
+
+
 def to_uint8(x):
     """clip_unnormalize_to_zero_to_255 (diffusion_utils/util.py:99-100)"""
     if x.device.type != "cuda" or x.numel() == 0:
@@ -775,7 +903,7 @@ def to_uint8(x):
 
 class LatentDiffusion(nn.Module):
     """diffusion/ddpm.py:24-126 (parameterization eps|x0, loss l1|l2|huber; samplers native, ddim, plms and pndm --
-    the reference's 'tero' fails inside its own p_sample_loop)"""
+    the reference's 'tero' fails inside its own p_sample_loop; 'dpmsolver' is this project's own)"""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -788,6 +916,7 @@ class LatentDiffusion(nn.Module):
             "plms": DDIMSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device, sampler_type="plms"),
             "pndm": PNDM_Sampler(ddpm_num_timesteps=h.num_timesteps, beta_start=h.linear_start, beta_end=h.linear_end,
                                  beta_schedule=h.beta_schedule, device=h.device),
+            "dpmsolver": DPMSolverSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device),      # not in the reference
         }
 
     def set_denoise_fn(self, denoise_fn, denoise_sample_fn):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Wall clock of whole sampling trajectories at C2 (unet_fast ch128, 64x64, bs 40 -> UNet batch 80, w=2) through
-LatentDiffusion.p_sample_loop on the captured step: DDIM-50, PNDM-50 (12 Runge-Kutta + 47 multistep evaluations) and, for
-reference, native-1000.  Each trajectory: one untimed run first (engine, packed weights, captured step), then `--reps`
-timed runs, synchronised, best and median kept.  Writes profiles/pndm_vs_ddim_c2.txt.
+LatentDiffusion.p_sample_loop on the captured step: DDIM-50, PNDM-50 (12 Runge-Kutta + 47 multistep evaluations),
+DPM-Solver++(2M) at 20 steps and, for reference, native-1000 (`--native-reps 0` leaves it out).  Each trajectory: one untimed
+run first (engine, packed weights, captured step), then `--reps` timed runs, synchronised, best and median kept.  Writes
+profiles/dpmsolver_vs_ddim_c2.txt (profiles/pndm_vs_ddim_c2.txt is the recording of the tool before it had the dpmsolver leg).
 
     python tools/bench_samplers.py [--prec f16x3] [--reps 3] [--native-reps 1]
 """
@@ -25,7 +26,7 @@ def main():
     ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3", "bf16x3", "f16", "bf16"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--native-reps", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pndm_vs_ddim_c2.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dpmsolver_vs_ddim_c2.txt"))
     a = ap.parse_args()
     from sgdm_amd.diffusion import LatentDiffusion
     wl = bench.WORKLOADS["c2"]
@@ -36,7 +37,10 @@ def main():
     dkw = dict(cond=data["cond"].cuda(), layout=None, cond_scale=2.0)
     x_T = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(23)).cuda()
     rows = []
-    for method, steps, evals, reps in (("ddim", 50, 50, a.reps), ("pndm", 50, 59, a.reps), ("native", 1000, 1000, a.native_reps)):
+    for method, steps, evals, reps in (("ddim", 50, 50, a.reps), ("pndm", 50, 59, a.reps), ("dpmsolver", 20, 20, a.reps),
+                                       ("native", 1000, 1000, a.native_reps)):
+        if reps < 1:
+            continue
         skw = dict(sampling_method=method, vis=None, num_timesteps=steps, ddim_eta=0.0, log_num_per_prog=10, clip_denoised=True,
                    dtp=1, temperature=1.0, noise_dropout=0, random_sample_condition=False, return_inter_dict=True,
                    disable_tqdm=True, hip_graph=True)
@@ -56,6 +60,8 @@ def main():
                 torch.cuda.synchronize()
                 secs.append(time.perf_counter() - t0)
         assert u8.dtype == torch.uint8
+        if method == "dpmsolver":       # de-duplicated times would mean fewer evaluations than steps
+            assert len(diff.sampler_list[method].plan(dict(skw, alphas_cumprod=diff.sampler.alphas_cumprod))[0]) == evals
         rows.append((method, steps, evals, min(secs), statistics.median(secs), len(secs)))
         print(rows[-1], flush=True)
     ddim_ms = rows[0][3] * 1e3 / rows[0][2]
@@ -66,6 +72,7 @@ def main():
     for method, steps, evals, best, med, n in rows:
         ms = best * 1e3 / evals
         lines.append(f"{method:10s} {steps:6d} {evals:10d} {best:20.3f} {med:8.3f} {n:5d} {ms:15.3f} {ms / ddim_ms - 1:+15.2%}")
+    lines.append("# best-to-median spread of s/trajectory: " + ", ".join(f"{r[0]} {r[4] / r[3] - 1:.2%}" for r in rows))
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:

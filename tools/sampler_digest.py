@@ -62,6 +62,7 @@ def main():
             run(f"{name} native-short {g}", diff, "native", skw(1000, hip_graph=graph), dkw, **short)
             run(f"{name} ddim-10 {g}", diff, "ddim", skw(10, hip_graph=graph), dkw)
             run(f"{name} pndm-10 {g}", diff, "pndm", skw(10, hip_graph=graph), dkw)
+            run(f"{name} dpmsolver-10 {g}", diff, "dpmsolver", skw(10, hip_graph=graph), dkw)
         run(f"{name} plms-10 eager", diff, "plms", skw(10), dkw)
         # eager only: what the captured step leaves out
         x_T = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(8)) * 1.7
@@ -80,7 +81,7 @@ def main():
         plain = LatentDiffusion(device="cuda", **bench.MODEL_PARAMS)
         plain.set_denoise_fn(m.forward, lambda x, t, **kw: m.forward_with_cond_scale(x, t, **kw))
         for method, sk, extra in (("native", skw(1000), short), ("ddim", skw(10), {}), ("plms", skw(10), {}),
-                                  ("pndm", skw(10), {}), ("ddim", skw(10, dtp=0.9), {})):
+                                  ("pndm", skw(10), {}), ("dpmsolver", skw(10), {}), ("ddim", skw(10, dtp=0.9), {})):
             run(f"{name} {method} plain-callable dtp={sk['dtp']}", plain, method, sk, dkw, **extra)
 
 
