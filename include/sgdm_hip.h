@@ -409,6 +409,18 @@ typedef struct sgd_dpmpp_row {
 } sgd_dpmpp_row;
 int sgd_dpmpp_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, float w, const sgd_dpmpp_row* row_dev,
                    float* x0_hist, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out, void* stream);
+/* v-prediction, sampling side (parameterization 'v', Salimans & Ho 2022: v = sa * noise - s1 * x_start with sa = sqrt(ac),
+ * s1 = sqrt(1 - ac); no counterpart in the reference): the network output read as v, guided, and changed to the eps the
+ * update kernels above read.  Guidance is linear in the network output, so it commutes with the change of variables:
+ *   v_g = guided(v_out)                      (the three cfg_mode forms above, each product rounded before it is added)
+ *   eps_out[n, p, cc] = sa[t[n]] * v_g + s1[t[n]] * x[n, cc, p]
+ * v_out is laid out like eps_nhwc ([2b, hw, c] when cfg_mode != 0, else [b, hw, c]), x is NCHW [b, c, hw], eps_out is
+ * [b, hw, c]: the update kernel that follows reads it with cfg_mode = 0.  (A guided NCHW output is b*c one-channel planes:
+ * c = 1, one t per plane.)  t is DEVICE int64 [b], the tables are the fp32 schedule buffers of sgd_q_sample: no host scalar
+ * changes between steps, so one captured step replays for every step.  eps_out must not alias x or v_out.  Additive entry
+ * (ABI unchanged at 24). */
+int sgd_v_to_eps(const float* x, const float* v_out, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+                 int32_t cfg_mode, float w, int32_t b, int32_t c, int32_t hw, float* eps_out, void* stream);
 /* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s
@@ -602,6 +614,11 @@ int sgd_linear_attention_bwd(const float* q, int32_t q_ld, int32_t q_hs, const f
  *   x_noisy = sa[t]*x0 + s1ma[t]*noise      (NCHW in, NCHW out; tables are the float32 schedule buffers) */
 int sgd_q_sample(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                  int32_t b, int64_t chw, float* out, void* stream);
+/* the same pass for parameterization 'v' (no counterpart in the reference): one read of x0 and noise gives
+ *   x_noisy = sa[t]*x0 + s1ma[t]*noise      (the bits of sgd_q_sample)
+ *   v       = sa[t]*noise - s1ma[t]*x0      (the training target; each product rounded before the subtraction) */
+int sgd_q_sample_v(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+                   int32_t b, int64_t chw, float* x_noisy_out, float* v_out, void* stream);
 /* --------------------------------------------------------------------------------------
  * The UNet stem (openaimodel.py:560-566, openaimodel_ca.py:735-741: a 3x3 convolution of the 3- or 4-channel input,
  * stride 1, padding 1) as a plain fp32 kernel (ABI 14): x NHWC [n,h,w,cin], cin 3 or 4; w the PARAMETER itself,

@@ -33,6 +33,8 @@ FILE_FLAGS = {"igemm.hip": ["-fno-slp-vectorize"], "pack.hip": ["-fno-slp-vector
 FILE_FLAGS["pndm.hip"] = ["-ffp-contract=off"]
 # dpm.hip: the same -- the DPM-Solver++ update is bit-equal to its torch-fp32 restatement only product by product
 FILE_FLAGS["dpm.hip"] = ["-ffp-contract=off"]
+# vpred.hip: the same -- the v target and the v -> eps change of variables, product by product
+FILE_FLAGS["vpred.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

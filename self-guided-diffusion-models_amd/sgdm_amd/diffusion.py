@@ -6,7 +6,9 @@ Mirrors (reference, /root/reference):
     diffusion/sampler/ddim_plms_sampler.py:25-391 DDIMSampler     ('ddim', 'plms')
     diffusion/sampler/pndm_sampler.py:13-211      PNDM_Sampler    ('pndm', include/sgdm_hip.h: sgd_pndm_step)
     dynamic/diffusionmodules/util.py:23-74        schedules / DDIM tables (deterministic host math)
-Without a counterpart there: DPMSolverSampler ('dpmsolver', DPM-Solver++(2M), include/sgdm_hip.h: sgd_dpmpp_step).
+Without a counterpart there: DPMSolverSampler ('dpmsolver', DPM-Solver++(2M), include/sgdm_hip.h: sgd_dpmpp_step) and
+parameterization='v' (Salimans & Ho 2022; include/sgdm_hip.h: sgd_q_sample_v, sgd_v_to_eps): the network output read as
+v is changed to a guided eps right after the UNet evaluation (``_StepRunner.v_to_eps``), every update kernel runs unchanged.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -88,15 +90,35 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-class _StepRunner:
-    """one sampling step = UNet(2B) + one fused update kernel"""
+def _v_tables(sk, dev):
+    """(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod) as fp32 device tables when the sampling kwargs say
+    parameterization='v', else None ('eps', the default of a direct sampler call, and 'x0' convert nothing).
+    ``p_sample_loop`` hands over the training schedule's buffers; a direct caller that passes only ``alphas_cumprod`` gets
+    the square roots formed from it in double and rounded once (the fp32 ``alphas_cumprod`` resolves 1 - ac to ~6e-4 at
+    t = 0, where the schedule's own table was rounded from float64: pass the tables where that matters)"""
+    par = (sk or {}).get("parameterization", "eps")
+    if par != "v":
+        if par not in ("eps", "x0"):
+            raise NotImplementedError(f"parameterization '{par}'")
+        return None
+    sa, s1 = sk.get("sqrt_alphas_cumprod"), sk.get("sqrt_one_minus_alphas_cumprod")
+    if sa is None or s1 is None:
+        ac = sk["alphas_cumprod"].detach().double()
+        sa, s1 = ac.sqrt(), (1.0 - ac).sqrt()
+    return tuple(a.detach().to(dev, torch.float32).contiguous() for a in (sa, s1))
 
-    def __init__(self, denoise_sample_fn, kwargs):
+
+class _StepRunner:
+    """one sampling step = UNet(2B) + one fused update kernel (+ the v -> eps pass between them when ``sk`` says
+    parameterization='v')"""
+
+    def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
         self.fn = denoise_sample_fn
         self.kwargs = dict(kwargs)
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
         self.lib = L.load()
         self._drop = {}
+        self.v = _v_tables(sk, dev)
 
     def fused_cfg(self):
         """whether a step takes the batch-doubled evaluation whose guided score is formed inside the step kernel: the
@@ -124,9 +146,25 @@ class _StepRunner:
             has_mask, p = self.drop_mask(B, x.device)
             mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
             eng = m._run(x, t, self.kwargs.get("cond"), self.kwargs.get("layout"), mask, 2 * B)
-            return eng.eps_nhwc, m._scale_mode(), float(self.kwargs["cond_scale"]), B, Cc
-        e = self.fn(x, t, **self.kwargs)            # generic path: guided eps, NCHW
-        return e.contiguous(), 0, 0.0, B * Cc, 1
+            mode, w = m._scale_mode(), float(self.kwargs["cond_scale"])
+            if self.v is None:
+                return eng.eps_nhwc, mode, w, B, Cc
+            out = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
+            return self.v_to_eps(x, eng.eps_nhwc, t, mode, w, B, Cc, out, _stream()), 0, 0.0, B, Cc
+        e = self.fn(x, t, **self.kwargs).contiguous()       # generic path: guided output, NCHW
+        if self.v is not None:
+            # B*C one-channel planes, one time per plane
+            e = self.v_to_eps(x, e.float(), t.repeat_interleave(Cc), 0, 0.0, B * Cc, 1, torch.empty_like(x), _stream())
+        return e, 0, 0.0, B * Cc, 1
+
+    def v_to_eps(self, x, v, t, mode, w, b, c, out, st, tables=None):
+        """parameterization 'v': the network output ``v`` (laid out as the step kernels read an eps with ``mode``) guided and
+        changed to eps = sa[t] v_g + s1[t] x at the time ``t`` [b] the UNet was evaluated at; ``out`` is read with mode 0
+        (``tables``: a captured step's static copies of the two schedule tables)"""
+        sa, s1 = tables or self.v
+        L.check(self.lib.sgd_v_to_eps(_ptr(x), _ptr(v), _ptr(t), _ptr(sa), _ptr(s1), mode, w, b, c, x.numel() // (b * c),
+                                      _ptr(out), st), "sgd_v_to_eps")
+        return out
 
 
 def _start_image(shape, x_T, dev, copy=False):
@@ -145,7 +183,7 @@ def _t_rows(times, B, dev):
 class _GraphedStep:
     """One CFG sampling step -- UNet at 2B (~135 launches) + the fused update -- captured into a hipGraph
     (``torch.cuda.CUDAGraph`` capture of the stream the C-ABI launchers are given), cached on the model per
-    (batch, resolution, precision, guidance, sampler) and replayed per step.
+    (batch, resolution, precision, guidance, sampler, parameterization) and replayed per step.
 
     Everything a step varies lives in fixed device buffers the captured kernels read: ``img`` (updated in place by
     ``sgd_*_step_dev``), ``t`` [B], ``coef`` (row of the per-step table), ``z`` and the cond-drop mask.  The RNG draws
@@ -168,8 +206,10 @@ class _GraphedStep:
         sig = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         prec = L.PREC_BY_NAME[m.hip_precision]
         eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec)
+        # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
+        par = "eps" if runner.v is None else ("v", runner.v[0].numel())
         key = (id(eng), tuple(img.shape), kind, clip, float(temperature), float(kw["cond_scale"]), m._scale_mode(),
-               sig(cond), sig(layout))
+               sig(cond), sig(layout), par)
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)
         if g is None:
@@ -181,7 +221,7 @@ class _GraphedStep:
                 del cache[k]                                # oldest first (dicts keep insertion order): a sweep over
                                                             # guidance weights / temperatures must not grow without bound
             g = cache[key] = cls(runner, eng, img, kind, clip, temperature)
-        g.begin(img, cond, layout, times, tab)
+        g.begin(img, cond, layout, times, tab, runner.v)
         return g
 
     def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
@@ -208,6 +248,9 @@ class _GraphedStep:
         self._inputs = eng._keep_inputs                 # the captured launches read these buffers on every replay
         img = self.img
         w, mode = float(kw["cond_scale"]), m._scale_mode()
+        # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
+        self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
+        self.veps = None if runner.v is None else torch.empty((B, hw, Cc), device=dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -218,29 +261,35 @@ class _GraphedStep:
             with torch.cuda.graph(self.graph, stream=side):
                 st = torch.cuda.current_stream(dev).cuda_stream
                 eng.launch(st)
-                self._launch_update(st, img, mode, w, B, Cc, hw, kind, clip, temperature)
+                eps = eng.eps_nhwc
+                if self.v is not None:                  # v -> guided eps at this step's time; the update reads it with mode 0
+                    eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
+                self._launch_update(st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature)
         torch.cuda.current_stream(dev).wait_stream(side)
 
-    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
-        """the update kernel of the captured step (reads the UNet's eps from the engine, updates img in place)"""
-        eng = self.eng
+    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
+        """the update kernel of the captured step (reads ``eps``: the UNet's output in the engine, or the converted eps of
+        parameterization 'v'; updates img in place)"""
         if kind == "ddpm":
-            L.check(self.lib.sgd_ddpm_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
+            L.check(self.lib.sgd_ddpm_step_dev(_ptr(img), _ptr(eps), _ptr(self.z), mode, w, _ptr(self.coef),
                                                clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st), "sgd_ddpm_step_dev")
         else:
-            L.check(self.lib.sgd_ddim_step_dev(_ptr(img), _ptr(eng.eps_nhwc), _ptr(self.z), mode, w, _ptr(self.coef),
+            L.check(self.lib.sgd_ddim_step_dev(_ptr(img), _ptr(eps), _ptr(self.z), mode, w, _ptr(self.coef),
                                                float(temperature), clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st),
                     "sgd_ddim_step_dev")
 
-    def begin(self, img, cond, layout, times, tab):
-        """start of a trajectory: x_T, the guidance tensors and the trajectory's tables (UNet time and coefficient row per
-        schedule row) into device buffers; packed weights re-checked"""
+    def begin(self, img, cond, layout, times, tab, v=None):
+        """start of a trajectory: x_T, the guidance tensors, the trajectory's tables (UNet time and coefficient row per
+        schedule row) and, for parameterization 'v', the two schedule tables into device buffers; packed weights re-checked"""
         self.eng.refresh(torch.cuda.current_stream().cuda_stream)
         self.img.copy_(img)
         if self.cond is not None:
             self.cond.copy_(cond)
         if self.layout is not None:
             self.layout.copy_(layout)
+        if self.v is not None:
+            for dst, src in zip(self.v, v):
+                dst.copy_(src)
         self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
 
     def step(self, i, noise=None, want_x0=True):
@@ -276,8 +325,8 @@ class _GraphedPNDMStep(_GraphedStep):
         self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
         super().__init__(runner, eng, img, kind, clip, temperature)
 
-    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
-        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.coef), _ptr(self.acc),
+    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
+        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(eps), mode, w, _ptr(self.coef), _ptr(self.acc),
                                        _ptr(self.base), _ptr(self.ring), B, Cc, hw, _ptr(img), st), "sgd_pndm_step")
 
 
@@ -290,8 +339,8 @@ class _GraphedDPMStep(_GraphedStep):
     COEF = (8, torch.float32)
     NOISE = False
 
-    def _launch_update(self, st, img, mode, w, B, Cc, hw, kind, clip, temperature):
-        L.check(self.lib.sgd_dpmpp_step(_ptr(img), _ptr(self.eng.eps_nhwc), mode, w, _ptr(self.coef), _ptr(self.x0), clip,
+    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
+        L.check(self.lib.sgd_dpmpp_step(_ptr(img), _ptr(eps), mode, w, _ptr(self.coef), _ptr(self.x0), clip,
                                         B, Cc, hw, _ptr(img), st), "sgd_dpmpp_step")
 
 
@@ -333,8 +382,9 @@ class _EagerStep:
             z = torch.nn.functional.dropout(z, p=self.noise_dropout)
         x0, ddpm = self.x0 if want_x0 else None, self.kind == "ddpm"
         if self.rank is not None:
-            # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C]
-            e4 = e if mode else e.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
+            # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C] (the layout is
+            # told by (bb, cc), not by the mode: the converted eps of parameterization 'v' is [B, hw, C] with mode 0)
+            e4 = e if (bb, cc) == (B, Cc) else e.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
             L.check(lib.sgd_x0_quantile(0 if ddpm else 1, _ptr(img), _ptr(e4), mode, w, coef, B, Cc, hw, *self.rank,
                                         _ptr(self.s_dyn), _stream()), "sgd_x0_quantile")
             if ddpm:
@@ -481,7 +531,9 @@ class Schedule_DDPM(nn.Module):
         reg("posterior_log_variance_clipped", to_torch(np.log(np.maximum(posterior_variance, 1e-20))))
         reg("posterior_mean_coef1", to_torch(betas * np.sqrt(alphas_cumprod_prev) / (1. - alphas_cumprod)))
         reg("posterior_mean_coef2", to_torch((1. - alphas_cumprod_prev) * np.sqrt(alphas) / (1. - alphas_cumprod)))
-        if h.parameterization == "eps":
+        if h.parameterization in ("eps", "v"):
+            # 'v' (not in the reference) takes the eps expression: no loss path consumes lvlb_weights (p_losses weighs every
+            # time alike), the buffer only has to exist
             lvlb = self.betas ** 2 / (2 * self.posterior_variance * to_torch(alphas) * (1 - self.alphas_cumprod))
         elif h.parameterization == "x0":
             lvlb = (0.5 * np.sqrt(torch.Tensor(alphas_cumprod)) / (2. * 1 - torch.Tensor(alphas_cumprod))).to(dev)
@@ -543,15 +595,19 @@ class Schedule_DDPM(nn.Module):
         h = self.hparams
         self.register_schedule(timesteps=timesteps, given_betas=h.given_betas, beta_schedule=h.beta_schedule,
                                linear_start=h.linear_start, linear_end=h.linear_end, cosine_s=h.cosine_s)
-        if h.parameterization not in ("eps", "x0"):
+        if h.parameterization not in ("eps", "x0", "v"):
             raise NotImplementedError()                                        # ddpm_sampler.py:162-163
         dev = self.betas.device
+        if sk.get("parameterization", h.parameterization) == "v" and "sqrt_alphas_cumprod" not in sk:
+            # a direct call: this object is the training schedule, so its own hparam and buffers stand in for the kwargs
+            sk = dict(sk, parameterization="v", sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
+                      sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         if type(temperature) == float or isinstance(temperature, int):
             temperature = [float(temperature)] * timesteps
         snaps = _Snapshots(timesteps, sk)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         stepper = _sampler_step(runner, sk, img, "ddpm", 1 if sk["clip_denoised"] else 0, range(timesteps),
                                 self.step_table(temperature))
         order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
@@ -607,7 +663,7 @@ class DDIMSampler(object):
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         stepper = _EagerStep(runner, img, "ddim", 1 if sk["clip_denoised"] else 0, self.ddim_timesteps, self.step_table, sk,
                              float(sk["temperature"]))
         B, Cc, hw = stepper.dims
@@ -615,7 +671,7 @@ class DDIMSampler(object):
 
         def guided(x, ts):
             eps, mode, w, bb, cc = runner.eps(x, ts)
-            if mode == 0:
+            if mode == 0 and cc == 1:               # one-channel planes: NCHW already (else [B, hw, C], whatever the mode)
                 return eps.reshape(shape).clone()
             out = torch.empty(shape, device=dev)
             L.check(runner.lib.sgd_cfg_combine(_ptr(eps), mode, w, bb, cc, hw, _ptr(out), _stream()), "sgd_cfg_combine")
@@ -694,7 +750,7 @@ class DDIMSampler(object):
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk, host=True)
-        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw), sk, img, "ddim", 1 if sk["clip_denoised"] else 0,
+        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw, sk, dev), sk, img, "ddim", 1 if sk["clip_denoised"] else 0,
                                 self.ddim_timesteps, self.step_table, float(sk["temperature"]))
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
@@ -786,7 +842,7 @@ class PNDM_Sampler(object):
         dev = torch.device(self.device)
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         # PNDM ignores dtp and noise_dropout: only the model / guidance conditions of the captured step apply
         if _graph_ok(runner, dict(sk, noise_dropout=0, dtp=1)):
             stepper = _GraphedPNDMStep.get(runner, img, "pndm", 0, times, tab)
@@ -806,7 +862,8 @@ class DPMSolverSampler(object):
     Sampling kwargs read: ``num_timesteps`` (S), ``alphas_cumprod``, ``clip_denoised``, ``log_num_per_prog``, and for direct
     callers ``dpm_spacing`` ('logsnr' | 'uniform' | 'quad', default 'logsnr'), ``dpm_order`` (1 | 2, default 2) and
     ``dpm_lower_order_final`` (default: fewer than 15 times).  ``ddim_eta``, ``temperature``, ``noise_dropout`` and ``vis`` are
-    ignored; ``dtp < 1`` is refused.  eps parameterization only, like 'ddim'.  Tests may inject ``x_T=``."""
+    ignored; ``dtp < 1`` is refused.  ``parameterization`` 'eps' (default; 'x0' is read as eps, like 'ddim' does) or 'v'.  Tests
+    may inject ``x_T=``."""
 
     def __init__(self, ddpm_num_timesteps, device):
         self.ddpm_num_timesteps = ddpm_num_timesteps
@@ -875,7 +932,7 @@ class DPMSolverSampler(object):
         dev = torch.device(self.device)
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {})
+        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         clip = 1 if sk["clip_denoised"] else 0
         total = len(ts)
         snaps = _Snapshots(total, sk)
@@ -903,7 +960,8 @@ def to_uint8(x):
 
 class LatentDiffusion(nn.Module):
     """diffusion/ddpm.py:24-126 (parameterization eps|x0, loss l1|l2|huber; samplers native, ddim, plms and pndm --
-    the reference's 'tero' fails inside its own p_sample_loop; 'dpmsolver' is this project's own)"""
+    the reference's 'tero' fails inside its own p_sample_loop; 'dpmsolver' and parameterization 'v'
+    are this project's own)"""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -943,7 +1001,11 @@ class LatentDiffusion(nn.Module):
     def p_sample_loop(self, sampling_method, shape, sampling_kwargs, **kwargs):
         sk = copy.deepcopy({k: v for k, v in sampling_kwargs.items()})
         sk.update(dict(alphas_cumprod=self.sampler.alphas_cumprod,
-                       alphas_cumprod_prev=self.sampler.alphas_cumprod_prev, betas=self.sampler.betas))
+                       alphas_cumprod_prev=self.sampler.alphas_cumprod_prev, betas=self.sampler.betas,
+                       parameterization=self.hparams.parameterization))
+        if self.hparams.parameterization == "v":        # the tables the v -> eps pass gathers from: the training schedule's
+            sk.update(dict(sqrt_alphas_cumprod=self.sampler.sqrt_alphas_cumprod,
+                           sqrt_one_minus_alphas_cumprod=self.sampler.sqrt_one_minus_alphas_cumprod))
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(
             shape=shape, denoise_sample_fn=self.denoise_sample_fn, sampling_kwargs=sk, **kwargs)

@@ -1026,15 +1026,27 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     h = diff.hparams
     noise = torch.randn_like(x_start) if noise is None else noise
     s = diff.sampler
+    if h.parameterization not in ("eps", "x0", "v"):
+        raise NotImplementedError()
+    v_target = None                     # parameterization 'v' (Salimans & Ho 2022): sa[t] * noise - s1[t] * x_start
     if x_start.device.type == "cuda":
         x_noisy = torch.empty_like(x_start)
         B = x_start.shape[0]
         x0, nz, tt = x_start.contiguous().float(), noise.contiguous().float(), t.contiguous().to(torch.int64)
-        L.check(lib.sgd_q_sample(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
-                                 _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy),
-                                 torch.cuda.current_stream().cuda_stream), "sgd_q_sample")
+        if h.parameterization == "v":   # x_noisy and the target from one read of x_start and noise
+            v_target = torch.empty_like(x_start)
+            L.check(lib.sgd_q_sample_v(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
+                                       _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy), _ptr(v_target),
+                                       torch.cuda.current_stream().cuda_stream), "sgd_q_sample_v")
+        else:
+            L.check(lib.sgd_q_sample(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
+                                     _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy),
+                                     torch.cuda.current_stream().cuda_stream), "sgd_q_sample")
     else:
         x_noisy = s.q_sample(original_sample=x_start, t=t, noise=noise)
+        if h.parameterization == "v":
+            v_target = (s._ext(s.sqrt_alphas_cumprod, t, x_start.shape) * noise
+                        - s._ext(s.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start)
     model_output, loss_inside, dict_inside = diff.denoise_fn(x_noisy, t, *args, **kwargs)
     prefix = "train" if diff.training else "val"
     loss_dict = {f"{prefix}/{k}": v for k, v in dict_inside.items()}
@@ -1043,7 +1055,7 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     elif h.parameterization == "eps":
         target = noise
     else:
-        raise NotImplementedError()
+        target = v_target
     if h.loss_type == "l2":
         loss = _MSEFn.apply(model_output, target)
     elif h.loss_type == "l1":
