@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define SGD_ABI_VERSION 24
+#define SGD_ABI_VERSION 25
 int sgd_abi_version(void);
 /* 16 hex digits identifying the sources and flags the library was compiled from (build.py: source_id()); static storage.
  * __graft_entry__.build() and tests/test_boundary_cpu.py compare it with the tree on disk. */
@@ -347,29 +347,30 @@ int sgd_fill_null_kv(const float* null_kv, int32_t batch, int32_t rows_per_b, in
  * ([cond ; uncond] halves, NHWC) when cfg_mode != 0, else at B.
  *   guided = cfg_mode 1 (imagen): (1-w)*eps_u + w*eps_c     (openaimodel.py:855)
  *            cfg_mode 2 (cfg)   : (1+w)*eps_c - w*eps_u     (openaimodel.py:857)
- * x, z, x_out, x0_out are NCHW [b,c,h,w].
- * DDPM ancestral step: ddpm_sampler.py:132-137,154-192.  coef = {sqrt_recip_ac, sqrt_recipm1_ac,
- * post_mean_coef1, post_mean_coef2, exp(0.5*post_log_var)*nonzero*temperature} for this t.
- * DDIM step: ddim_plms_sampler.py:346-391. coef = {sqrt_one_minus_at, 1/sqrt(a_t) is NOT used
- * (the reference divides by a_t.sqrt()), a_t, a_prev, sigma_t*temperature, 0}.
+ * x, z, x_out, x0_out are NCHW [b,c,h,w].  x_out == x is allowed (every update is elementwise); x0_out may be NULL.
+ *
+ * Every step reads what changes between steps -- its row of the trajectory's table -- from DEVICE memory, so one sampling
+ * step = UNet program + one of these launches has no by-value argument that changes between steps: it can be captured into
+ * a hipGraph once and replayed, and the eager loop uses the same entry with a row address of the uploaded table
+ * (sgdm_amd/diffusion.py: _GraphedStep / _EagerStep; reference loops: ddpm_sampler.py:194-238,
+ * ddim_plms_sampler.py:302-344).
+ *
+ * clip / dyn_s (DDPM, DDIM): dyn_s == NULL: clip != 0 clamps x0 to [-1, 1] (clip_x0_minus_one_to_one, dtp == 1).
+ * dyn_s != NULL (DEVICE [b], from sgd_x0_quantile below): dynamic thresholding, x0 = clamp(x0, -s, s) / s with s = dyn_s[n];
+ * clip is ignored.
  * -------------------------------------------------------------------------------------- */
+/* DDPM ancestral step (ddpm_sampler.py:132-137,154-192).  coef_dev = {sqrt_recip_ac, sqrt_recipm1_ac, post_mean_coef1,
+ * post_mean_coef2, exp(0.5*post_log_var)*nonzero*temperature} for this t:
+ *   x0 = k0 x - k1 e;  clip / dyn_s;  x_out = k2 x0 + k3 x + k4 z */
 int sgd_ddpm_step(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                  const float* coef /* HOST [5] */, int32_t clip, int32_t b, int32_t c, int32_t hw,
-                  float* x_out, float* x0_out, void* stream);
+                  const float* coef_dev /* DEVICE [5] */, int32_t clip, const float* dyn_s /* DEVICE [b] or NULL */,
+                  int32_t b, int32_t c, int32_t hw, float* x_out, float* x0_out, void* stream);
+/* DDIM step (ddim_plms_sampler.py:346-391).  coef_dev = {sqrt(1 - a_t), a_t, a_prev, sigma_t, unused} for this index:
+ *   x0 = (x - k0 e) / sqrt(a_t);  clip / dyn_s;  x_out = sqrt(a_prev) x0 + sqrt(1 - a_prev - sigma_t^2) e + sigma_t z temperature */
 int sgd_ddim_step(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                  const float* coef /* HOST [4]: sqrt_one_minus_at, a_t, a_prev, sigma_t */, float temperature,
-                  int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out, float* x0_out, void* stream);
-/* The same two steps with the per-step coefficients read from DEVICE memory (coef_dev[5] / coef_dev[4], same meaning as
- * above) and x updated IN PLACE (x_out == x allowed: the update is elementwise).  With the UNet inputs (x, t) and these
- * coefficients in fixed device buffers, one sampling step = UNet program + this launch has no by-value argument that
- * changes between steps, so it can be captured into a hipGraph once per trajectory and replayed
- * (sgdm_amd/diffusion.py: _GraphedStep; reference loop: ddpm_sampler.py:194-238, ddim_plms_sampler.py:302-344). */
-int sgd_ddpm_step_dev(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                      const float* coef_dev, int32_t clip, int32_t b, int32_t c, int32_t hw,
-                      float* x_out, float* x0_out, void* stream);
-int sgd_ddim_step_dev(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                      const float* coef_dev, float temperature, int32_t clip, int32_t b, int32_t c, int32_t hw,
-                      float* x_out, float* x0_out, void* stream);
+                  const float* coef_dev /* DEVICE [5] */, float temperature, int32_t clip,
+                  const float* dyn_s /* DEVICE [b] or NULL */, int32_t b, int32_t c, int32_t hw, float* x_out, float* x0_out,
+                  void* stream);
 /* PNDM update (pndm_sampler.py:96-141, F-PNDM: four Runge-Kutta sub-steps x 3, then 4th-order linear multistep): ONE
  * launch per UNet evaluation.  Everything that changes between evaluations is read from DEVICE memory -- the row below,
  * the accumulator `acc`, the warm-up start image `base` and the history `ring` [3][b*c*hw] -- so one captured step
@@ -424,18 +425,12 @@ int sgd_v_to_eps(const float* x, const float* v_out, const int64_t* t, const flo
 /* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s
- * sgd_x0_quantile forms x0 like the step kernels (kind 0: DDPM coef[5], kind 1: DDIM coef[4]) and selects the two order
- * statistics lo / hi of |x0| per sample (exact radix select), interpolating with frac like torch.quantile;
- * the *_dyn steps are sgd_ddpm_step / sgd_ddim_step with that per-sample scale instead of the static clip. */
+ * sgd_x0_quantile forms x0 like the step kernels from the same DEVICE row (kind 0: DDPM, kind 1: DDIM) and selects the two
+ * order statistics lo / hi of |x0| per sample (exact radix select), interpolating with frac like torch.quantile; the step
+ * that follows takes s_out as its dyn_s. */
 int sgd_x0_quantile(int32_t kind, const float* x, const float* eps_nhwc, int32_t cfg_mode, float w,
-                    const float* coef /* HOST */, int32_t b, int32_t c, int32_t hw, int32_t lo, int32_t hi, float frac,
-                    float* s_out /* [b] */, void* stream);
-int sgd_ddpm_step_dyn(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                      const float* coef /* HOST [5] */, const float* dyn_s, int32_t b, int32_t c, int32_t hw,
-                      float* x_out, float* x0_out, void* stream);
-int sgd_ddim_step_dyn(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                      const float* coef /* HOST [4] */, float temperature, const float* dyn_s, int32_t b, int32_t c,
-                      int32_t hw, float* x_out, float* x0_out, void* stream);
+                    const float* coef_dev /* DEVICE [5] */, int32_t b, int32_t c, int32_t hw, int32_t lo, int32_t hi,
+                    float frac, float* s_out /* [b] */, void* stream);
 
 /* pooled guidance token of the token-guidance path (cond_token_num > 1, openaimodel_ca.py:999-1004):
  * cond [n, tokens, c] -> out [n, c] = cond[:, 0, :] (cls = 1, use_cls_token_as_pooled) or mean over tokens (cls = 0) */

@@ -5,20 +5,10 @@
 // it is added, so the update is a fixed sequence of correctly rounded IEEE fp32 adds and multiplies that a torch-fp32
 // restatement reproduces bit for bit (tests/test_hip_dpmsolver.py).  All scalars come from the host (float64, rounded once):
 // no division and no sqrt on the device.
-#include "sgdm_common.h"
+#include "sampler_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
-
-// guided eps of openaimodel.py:855/857, un-contracted (the forms of pndm.hip's pndm_guided)
-__device__ __forceinline__ float dpm_guided(const float* __restrict__ eps, int cfg_mode, float w, int b, int n, int c, int hw,
-                                            int cc, int p) {
-    const float ec = eps[((long)n * hw + p) * c + cc];
-    if (cfg_mode == 0) return ec;
-    const float eu = eps[((long)(n + b) * hw + p) * c + cc];
-    if (cfg_mode == 1) return (1.f - w) * eu + w * ec;
-    return (1.f + w) * ec - w * eu;
-}
 
 // x / x_out carry no __restrict__: the update may run in place
 __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const float* __restrict__ eps, int cfg_mode, float w,
@@ -28,10 +18,8 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= count) return;
     const float s1ma = row->s1ma, rsa = row->rsa, A = row->A, B = row->B, kc = row->cc, kp = row->cp;
-    const int p = i % hw;
-    const long t = i / hw;
-    const int cc = t % c, n = t / c;
-    const float e = dpm_guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
+    const auto [n, cc, p] = nchw_split(i, c, hw);
+    const float e = guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
     const float xi = x[i];
     float x0 = (xi - s1ma * e) * rsa;                       // data prediction
     if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
@@ -40,8 +28,6 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(const float* x, const f
     x0_hist[i] = x0;
     x_out[i] = A * xi + B * D;
 }
-
-inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // Small boundary / sampler kernels (gfx950).  All element-wise, HBM- or launch-bound.
-#include "sgdm_common.h"
+#include "sampler_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
@@ -190,31 +190,24 @@ __global__ void fill_null_kv_kernel(const float* __restrict__ null_kv, int batch
     kv[((long)b * rows_per_b + row) * 2 * d + j] = null_kv[j];      // [k(0:d) | v(d:2d)] == null_kv[0], null_kv[1]
 }
 
-__device__ __forceinline__ float guided(const float* __restrict__ eps, int cfg_mode, float w, int b, int n, int c,
-                                        int hw, int cc, int p) {
-    const float ec = eps[((long)n * hw + p) * c + cc];
-    if (cfg_mode == 0) return ec;
-    const float eu = eps[((long)(n + b) * hw + p) * c + cc];
-    if (cfg_mode == 1) return (1.f - w) * eu + w * ec;        // imagen  (openaimodel.py:855)
-    return (1.f + w) * ec - w * eu;                           // cfg     (openaimodel.py:857)
+struct Coef5 { float v[5]; };                                 // one row of a trajectory's table, in device memory
+
+// A product that is rounded on its own: the empty asm hides it from the vectoriser and from -ffp-contract=fast, so the add
+// that uses it cannot absorb it.  ddpm_step_kernel's last two lines need it: which of their products the compiler fuses
+// depends on how it pairs them, and the validated DDPM trajectories are the ones with k2 * x0 and k4 * z rounded.
+__device__ __forceinline__ float rounded(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
 }
 
-struct Coef5 { float v[5]; };
-
 // x / x_out carry no __restrict__: the graph-replayed form updates x in place
-__global__ void ddpm_step_kernel(const float* x, const float* __restrict__ eps,
-                                 const float* __restrict__ z, int cfg_mode, float w, Coef5 k, const float* kdev, int clip,
-                                 int b, int c, int hw, float* x_out, float* __restrict__ x0_out,
-                                 const float* __restrict__ dyn_s) {
+__global__ void ddpm_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ z, int cfg_mode,
+                                 float w, const Coef5* __restrict__ row, int clip, int b, int c, int hw, float* x_out,
+                                 float* __restrict__ x0_out, const float* __restrict__ dyn_s) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= (long)b * c * hw) return;
-    if (kdev) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) k.v[j] = kdev[j];
-    }
-    const int p = i % hw;
-    const long t = i / hw;
-    const int cc = t % c, n = t / c;
+    const Coef5 k = *row;
+    const auto [n, cc, p] = nchw_split(i, c, hw);
     const float e = guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
     const float xv = x[i];
     float x0 = k.v[0] * xv - k.v[1] * e;                      // predict_start_from_noise (ddpm_sampler.py:132-137)
@@ -222,24 +215,18 @@ __global__ void ddpm_step_kernel(const float* x, const float* __restrict__ eps,
         const float s = dyn_s[n];
         x0 = fminf(fmaxf(x0, -s), s) / s;
     } else if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);        // clip_x0_minus_one_to_one, dtp == 1
-    const float mean = k.v[2] * x0 + k.v[3] * xv;             // q_posterior (ddpm_sampler.py:121-125)
-    x_out[i] = mean + k.v[4] * z[i];                          // :190-191, k4 = nonzero*exp(.5 logvar)*temperature
+    const float mean = rounded(k.v[2] * x0) + k.v[3] * xv;    // q_posterior (ddpm_sampler.py:121-125): fma(k3, xv, k2 * x0)
+    x_out[i] = mean + rounded(k.v[4] * z[i]);                 // :190-191, k4 = nonzero*exp(.5 logvar)*temperature
     if (x0_out) x0_out[i] = x0;
 }
 
-__global__ void ddim_step_kernel(const float* x, const float* __restrict__ eps,
-                                 const float* __restrict__ z, int cfg_mode, float w, Coef5 k, const float* kdev,
-                                 float temperature, int clip, int b, int c, int hw, float* x_out,
-                                 float* __restrict__ x0_out, const float* __restrict__ dyn_s) {
+__global__ void ddim_step_kernel(const float* x, const float* __restrict__ eps, const float* __restrict__ z, int cfg_mode,
+                                 float w, const Coef5* __restrict__ row, float temperature, int clip, int b, int c, int hw,
+                                 float* x_out, float* __restrict__ x0_out, const float* __restrict__ dyn_s) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= (long)b * c * hw) return;
-    if (kdev) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) k.v[j] = kdev[j];
-    }
-    const int p = i % hw;
-    const long t = i / hw;
-    const int cc = t % c, n = t / c;
+    const Coef5 k = *row;                                         // {sqrt(1 - a_t), a_t, a_prev, sigma_t, unused}
+    const auto [n, cc, p] = nchw_split(i, c, hw);
     const float e = guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
     const float s1m = k.v[0], a_t = k.v[1], a_prev = k.v[2], sigma = k.v[3];
     float x0 = (x[i] - s1m * e) / sqrtf(a_t);                 // ddim_plms_sampler.py:369-370
@@ -265,9 +252,7 @@ __global__ void cfg_combine_kernel(const float* __restrict__ eps, int cfg_mode, 
                                    float* __restrict__ out) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= (long)b * c * hw) return;
-    const int p = i % hw;
-    const long t = i / hw;
-    const int cc = t % c, n = t / c;
+    const auto [n, cc, p] = nchw_split(i, c, hw);
     out[i] = guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
 }
 
@@ -287,8 +272,6 @@ __global__ void geglu_kernel(const float* __restrict__ in, long rows, int inner,
     o.w = a.w * (0.5f * g.w * (1.0f + erff(g.w * 0.70710678118654752f)));
     *reinterpret_cast<float4*>(out + r * inner + c) = o;
 }
-
-inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
 
@@ -380,78 +363,25 @@ extern "C" int sgd_fill_null_kv(const float* null_kv, int32_t batch, int32_t row
     return sgd_check_launch();
 }
 
-static int ddpm_step_impl(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                          const float* coef, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
-                          float* x0_out, const float* dyn_s, void* stream) {
-    SGD_CLEAR_ERR();
-    if (!x || !eps_nhwc || !z || !coef || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2)
-        return SGD_ERR_ARG;
-    Coef5 k;
-    for (int i = 0; i < 5; ++i) k.v[i] = coef[i];
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc,
-                       z, cfg_mode, w, k, (const float*)nullptr, clip, b, c, hw, x_out, x0_out, dyn_s);
-    return sgd_check_launch();
-}
-
-extern "C" int sgd_ddpm_step_dev(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                                 const float* coef_dev, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
-                                 float* x0_out, void* stream) {
-    SGD_CLEAR_ERR();
-    if (!x || !eps_nhwc || !z || !coef_dev || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2)
-        return SGD_ERR_ARG;
-    Coef5 k = {};
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc,
-                       z, cfg_mode, w, k, coef_dev, clip, b, c, hw, x_out, x0_out, (const float*)nullptr);
-    return sgd_check_launch();
-}
-
-static int ddim_step_impl(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                          const float* coef, float temperature, int32_t clip, int32_t b, int32_t c, int32_t hw,
-                          float* x_out, float* x0_out, const float* dyn_s, void* stream) {
-    SGD_CLEAR_ERR();
-    if (!x || !eps_nhwc || !z || !coef || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2)
-        return SGD_ERR_ARG;
-    Coef5 k;
-    for (int i = 0; i < 4; ++i) k.v[i] = coef[i];
-    k.v[4] = 0.f;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc,
-                       z, cfg_mode, w, k, (const float*)nullptr, temperature, clip, b, c, hw, x_out, x0_out, dyn_s);
-    return sgd_check_launch();
-}
-
-extern "C" int sgd_ddim_step_dev(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                                 const float* coef_dev, float temperature, int32_t clip, int32_t b, int32_t c, int32_t hw,
-                                 float* x_out, float* x0_out, void* stream) {
-    SGD_CLEAR_ERR();
-    if (!x || !eps_nhwc || !z || !coef_dev || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2)
-        return SGD_ERR_ARG;
-    Coef5 k = {};
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc,
-                       z, cfg_mode, w, k, coef_dev, temperature, clip, b, c, hw, x_out, x0_out, (const float*)nullptr);
-    return sgd_check_launch();
-}
-
 extern "C" int sgd_ddpm_step(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                             const float* coef, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
-                             float* x0_out, void* stream) {
-    return ddpm_step_impl(x, eps_nhwc, z, cfg_mode, w, coef, clip, b, c, hw, x_out, x0_out, nullptr, stream);
-}
-extern "C" int sgd_ddim_step(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                             const float* coef, float temperature, int32_t clip, int32_t b, int32_t c, int32_t hw,
+                             const float* coef_dev, int32_t clip, const float* dyn_s, int32_t b, int32_t c, int32_t hw,
                              float* x_out, float* x0_out, void* stream) {
-    return ddim_step_impl(x, eps_nhwc, z, cfg_mode, w, coef, temperature, clip, b, c, hw, x_out, x0_out, nullptr, stream);
+    SGD_CLEAR_ERR();
+    if (!x || !eps_nhwc || !z || !coef_dev || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2) return SGD_ERR_ARG;
+    hipLaunchKernelGGL(ddpm_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, z,
+                       cfg_mode, w, reinterpret_cast<const Coef5*>(coef_dev), clip, b, c, hw, x_out, x0_out, dyn_s);
+    return sgd_check_launch();
 }
-extern "C" int sgd_ddpm_step_dyn(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                                 const float* coef, const float* dyn_s, int32_t b, int32_t c, int32_t hw, float* x_out,
-                                 float* x0_out, void* stream) {
-    if (!dyn_s) return SGD_ERR_ARG;
-    return ddpm_step_impl(x, eps_nhwc, z, cfg_mode, w, coef, 0, b, c, hw, x_out, x0_out, dyn_s, stream);
-}
-extern "C" int sgd_ddim_step_dyn(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
-                                 const float* coef, float temperature, const float* dyn_s, int32_t b, int32_t c, int32_t hw,
-                                 float* x_out, float* x0_out, void* stream) {
-    if (!dyn_s) return SGD_ERR_ARG;
-    return ddim_step_impl(x, eps_nhwc, z, cfg_mode, w, coef, temperature, 0, b, c, hw, x_out, x0_out, dyn_s, stream);
+
+extern "C" int sgd_ddim_step(const float* x, const float* eps_nhwc, const float* z, int32_t cfg_mode, float w,
+                             const float* coef_dev, float temperature, int32_t clip, const float* dyn_s, int32_t b, int32_t c,
+                             int32_t hw, float* x_out, float* x0_out, void* stream) {
+    SGD_CLEAR_ERR();
+    if (!x || !eps_nhwc || !z || !coef_dev || !x_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2) return SGD_ERR_ARG;
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(nblk((long)b * c * hw)), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, z,
+                       cfg_mode, w, reinterpret_cast<const Coef5*>(coef_dev), temperature, clip, b, c, hw, x_out, x0_out,
+                       dyn_s);
+    return sgd_check_launch();
 }
 
 // Dynamic thresholding scale (dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79): per sample
@@ -462,10 +392,11 @@ extern "C" int sgd_ddim_step_dyn(const float* x, const float* eps_nhwc, const fl
 // statistics, no sort, no atomics on global memory.
 template <int KIND>
 __global__ __launch_bounds__(256) void x0_quantile_kernel(const float* __restrict__ x, const float* __restrict__ eps,
-                                                          int cfg_mode, float w, Coef5 k, int b, int c, int hw, int lo,
-                                                          int hi, float frac, float* __restrict__ s_out) {
+                                                          int cfg_mode, float w, const Coef5* __restrict__ row, int b, int c,
+                                                          int hw, int lo, int hi, float frac, float* __restrict__ s_out) {
     __shared__ unsigned hist[256];
     __shared__ unsigned sel_prefix, sel_k;
+    const Coef5 k = *row;
     const int n = blockIdx.x, cnt = c * hw;
     auto key_of = [&](int j) -> unsigned {
         const int cc = j / hw, p = j - cc * hw;
@@ -512,13 +443,12 @@ __global__ __launch_bounds__(256) void x0_quantile_kernel(const float* __restric
 }
 
 extern "C" int sgd_x0_quantile(int32_t kind, const float* x, const float* eps_nhwc, int32_t cfg_mode, float w,
-                               const float* coef, int32_t b, int32_t c, int32_t hw, int32_t lo, int32_t hi, float frac,
+                               const float* coef_dev, int32_t b, int32_t c, int32_t hw, int32_t lo, int32_t hi, float frac,
                                float* s_out, void* stream) {
     SGD_CLEAR_ERR();
-    if (!x || !eps_nhwc || !coef || !s_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2) return SGD_ERR_ARG;
+    if (!x || !eps_nhwc || !coef_dev || !s_out || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2) return SGD_ERR_ARG;
     if (lo < 0 || hi < lo || hi >= c * hw || (kind != 0 && kind != 1)) return SGD_ERR_ARG;
-    Coef5 k = {};
-    for (int i = 0; i < (kind == 0 ? 5 : 4); ++i) k.v[i] = coef[i];
+    const Coef5* k = reinterpret_cast<const Coef5*>(coef_dev);
     if (kind == 0) hipLaunchKernelGGL((x0_quantile_kernel<0>), dim3(b), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, cfg_mode, w, k, b, c, hw, lo, hi, frac, s_out);
     else hipLaunchKernelGGL((x0_quantile_kernel<1>), dim3(b), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, cfg_mode, w, k, b, c, hw, lo, hi, frac, s_out);
     return sgd_check_launch();

@@ -6,23 +6,13 @@
 // -ffp-contract=fast, so the flag has to come from the command line.)  With the per-evaluation scalars formed on the host
 // from the reference's fp32 expressions in IEEE arithmetic, a step fed the reference's residual reproduces the reference's
 // image bit for bit.
-#include "sgdm_common.h"
+#include "sampler_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
 
 // the reference's Python constants 1/6, 1/3, 1/24 as torch casts them for an fp32 tensor (double -> nearest fp32)
 constexpr float K16 = 0x1.555556p-3f, K13 = 0x1.555556p-2f, K124 = 0x1.555556p-5f;
-
-// guided eps of openaimodel.py:855/857 (the semantics of misc.hip's guided(); here without contraction, like torch)
-__device__ __forceinline__ float pndm_guided(const float* __restrict__ eps, int cfg_mode, float w, int b, int n, int c,
-                                             int hw, int cc, int p) {
-    const float ec = eps[((long)n * hw + p) * c + cc];
-    if (cfg_mode == 0) return ec;
-    const float eu = eps[((long)(n + b) * hw + p) * c + cc];
-    if (cfg_mode == 1) return (1.f - w) * eu + w * ec;
-    return (1.f + w) * ec - w * eu;
-}
 
 // x / x_out carry no __restrict__: the update may run in place
 __global__ __launch_bounds__(256) void pndm_step_kernel(const float* x, const float* __restrict__ eps, int cfg_mode, float w,
@@ -36,10 +26,8 @@ __global__ __launch_bounds__(256) void pndm_step_kernel(const float* x, const fl
     const float d = row->d, c1 = row->c1, c2 = row->c2;
     // ring slots reduced mod 3: a malformed row can mix up the history but never address outside the ring
     const long s1 = (unsigned)row->slot1 % 3u, s2 = (unsigned)row->slot2 % 3u, s3 = (unsigned)row->slot3 % 3u;
-    const int p = i % hw;
-    const long t = i / hw;
-    const int cc = t % c, n = t / c;
-    const float e = pndm_guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
+    const auto [n, cc, p] = nchw_split(i, c, hw);
+    const float e = guided(eps, cfg_mode, w, b, n, c, hw, cc, p);
     float src, r;                                           // transfer(src, t, t_next, r)
     if (phase == SGD_PNDM_RK0) {                            // step_prk, t % 4 == 0 (cur_residual starts from int 0)
         src = x[i];
@@ -64,8 +52,6 @@ __global__ __launch_bounds__(256) void pndm_step_kernel(const float* x, const fl
     }
     x_out[i] = src + d * (c1 * src - c2 * r);               // Eq. 9 (pndm_sampler.py:137-141)
 }
-
-inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
 

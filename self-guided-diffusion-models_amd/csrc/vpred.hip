@@ -7,7 +7,7 @@
 // rounded before it is added, so a torch-fp32 restatement reproduces the outputs bit for bit (tests/test_hip_vpred.py).
 // x_noisy carries the bits of sgd_q_sample (csrc/backward.hip): that unit allows contraction, but its kernel is compiled to
 // one packed multiply of both products and an add, i.e. the same two rounded products; the test compares the two launches.
-#include "sgdm_common.h"
+#include "sampler_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
@@ -26,16 +26,6 @@ __global__ __launch_bounds__(256) void q_sample_v_kernel(const float* __restrict
     v[i] = a * ni - s * xi;
 }
 
-// guided network output of openaimodel.py:855/857, un-contracted (the forms of dpm.hip's dpm_guided)
-__device__ __forceinline__ float vp_guided(const float* __restrict__ v, int cfg_mode, float w, int b, int n, int c, int hw,
-                                           int cc, int p) {
-    const float vc = v[((long)n * hw + p) * c + cc];
-    if (cfg_mode == 0) return vc;
-    const float vu = v[((long)(n + b) * hw + p) * c + cc];
-    if (cfg_mode == 1) return (1.f - w) * vu + w * vc;
-    return (1.f + w) * vc - w * vu;
-}
-
 // one thread per PIXEL, looping over its channels.  x is hw-major (NCHW): per channel the 64 lanes of a wave read 256
 // consecutive bytes.  v and eps_out are c-minor: a lane touches c consecutive floats, a wave 64 * c * 4 consecutive bytes,
 // every byte of which it uses over the c iterations.  (One thread per element would be coalesced on one side only and
@@ -50,13 +40,11 @@ __global__ __launch_bounds__(256) void v_to_eps_kernel(const float* __restrict__
     const int64_t tt = t[n];
     const float a = sa[tt], s = s1[tt];
     for (int cc = 0; cc < c; ++cc) {
-        const float vg = vp_guided(v, cfg_mode, w, b, n, c, hw, cc, p);
+        const float vg = guided(v, cfg_mode, w, b, n, c, hw, cc, p);
         const float xi = x[((long)n * c + cc) * hw + p];
         eps_out[i * c + cc] = a * vg + s * xi;
     }
 }
-
-inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
 

@@ -22,7 +22,7 @@ PREC_F32, PREC_F16X3, PREC_BF16X3, PREC_F16, PREC_BF16 = 0, 1, 2, 3, 4
 PREC_BY_NAME = {"f32": PREC_F32, "f16x3": PREC_F16X3, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "bf16": PREC_BF16}
 # single-product modes (operands rounded once to 16 bits, one MFMA product per term): inference only -- train.py refuses them
 INFERENCE_ONLY = ("f16", "bf16")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 # sgd_igemm_args.tune (include/sgdm_hip.h: SGD_TUNE_*): per-call schedule overrides for parity tests and A/B tools
 TUNE_BN128, TUNE_BN256, TUNE_FLAT2, TUNE_DEFER, TUNE_PLAIN_SCHEDULE, TUNE_LN_PACKED, TUNE_NO_SMALL = 1, 2, 4, 8, 16, 32, 64
@@ -33,6 +33,17 @@ TUNE_NO_SUBPIXEL = 32768
 PACK_FORWARD, PACK_DGRAD, PACK_SUBPIXEL = 0, 1, 2
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+
+
+class dvp:
+    """argtype of a pointer the KERNEL dereferences where the entry once took a host array (the row of sgd_x0_quantile): an
+    address like ``vp``, but a ctypes array or pointer -- host memory -- is a TypeError here, not a GPU fault there"""
+
+    @staticmethod
+    def from_param(v):
+        if isinstance(v, (C.Array, C._Pointer)):
+            raise TypeError("a DEVICE address (tensor.data_ptr()) is expected, not host memory")
+        return vp.from_param(v)
 
 
 class IgemmArgs(C.Structure):
@@ -132,13 +143,9 @@ SIGNATURES = {
     "sgd_linear_sparse_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     "sgd_nhwc_to_nchw": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "sgd_fill_null_kv": (i32, [vp, i32, i32, i32, i32, vp, vp]),
-    "sgd_ddpm_step": (i32, [vp, vp, vp, i32, f32, C.POINTER(f32), i32, i32, i32, i32, vp, vp, vp]),
-    "sgd_ddim_step": (i32, [vp, vp, vp, i32, f32, C.POINTER(f32), f32, i32, i32, i32, i32, vp, vp, vp]),
-    "sgd_ddpm_step_dev": (i32, [vp, vp, vp, i32, f32, vp, i32, i32, i32, i32, vp, vp, vp]),
-    "sgd_ddim_step_dev": (i32, [vp, vp, vp, i32, f32, vp, f32, i32, i32, i32, i32, vp, vp, vp]),
-    "sgd_x0_quantile": (i32, [i32, vp, vp, i32, f32, C.POINTER(f32), i32, i32, i32, i32, i32, f32, vp, vp]),
-    "sgd_ddpm_step_dyn": (i32, [vp, vp, vp, i32, f32, C.POINTER(f32), vp, i32, i32, i32, vp, vp, vp]),
-    "sgd_ddim_step_dyn": (i32, [vp, vp, vp, i32, f32, C.POINTER(f32), f32, vp, i32, i32, i32, vp, vp, vp]),
+    "sgd_ddpm_step": (i32, [vp, vp, vp, i32, f32, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "sgd_ddim_step": (i32, [vp, vp, vp, i32, f32, vp, f32, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "sgd_x0_quantile": (i32, [i32, vp, vp, i32, f32, dvp, i32, i32, i32, i32, i32, f32, vp, vp]),
     "sgd_token_pool": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "sgd_geglu": (i32, [vp, i64, i32, vp, vp]),
     "sgd_to_uint8": (i32, [vp, i64, vp, vp]),

@@ -16,7 +16,6 @@ DDIM update + noise (include/sgdm_hip.h: sgd_ddpm_step / sgd_ddim_step).  RNG dr
 per-step mask uniform_ and z) are kept in the reference's order so seeded runs line up.
 """
 import copy
-import ctypes as C
 import os
 import warnings
 from functools import partial
@@ -180,25 +179,126 @@ def _t_rows(times, B, dev):
     return t.view(-1, 1).expand(len(t), B).contiguous()
 
 
+def _quantile_rank(dtp, count):
+    """(lo, hi, frac) of torch.quantile(., dtp) over `count` fp32 values: rank = q * (count - 1) in the input dtype,
+    linear interpolation between the order statistics floor(rank) and ceil(rank)"""
+    rank = torch.tensor(dtp, dtype=torch.float32) * (count - 1)
+    lo = torch.floor(rank)
+    return int(lo), int(torch.ceil(rank)), float(rank - lo)
+
+
+class _Update:
+    """One sampler's update kernel, as both step classes below drive it: the ONE place the kernel is launched from, the state
+    buffers it keeps between launches (``alloc``), the layout of a row of the trajectory's table (``COEF``) and what it
+    honours of the sampling kwargs -- ``NOISE``: it reads a ``z`` (drawn per step, at eta = 0 too); ``EXTRAS``: noise dropout
+    and dynamic thresholding (dtp < 1), which only the eager step runs.  ``launch`` reads its row from DEVICE memory; an
+    update with ``NOISE`` also takes ``z`` and ``want_x0`` (the others have no noise and no optional output)."""
+
+    COEF = None                 # (words, dtype) of one row: every update states its own
+    NOISE = False
+    EXTRAS = False
+    x0 = None                   # clipped x0 prediction of the last launch (snapshot steps clone it), where there is one
+
+    def __init__(self, kind, sk, clip, temperature=1.0):
+        self.lib, self.kind, self.clip, self.temperature = L.load(), kind, clip, float(temperature)
+        self.noise_dropout = sk.get("noise_dropout", 0) if self.EXTRAS else 0
+        self.dtp = sk.get("dtp", 1) if self.EXTRAS else 1
+
+
+class _DDUpdate(_Update):
+    """``sgd_ddpm_step`` (kind 'ddpm') / ``sgd_ddim_step`` ('ddim'): x0 prediction, clip or dynamic threshold, posterior /
+    DDIM update, noise.  Dynamic thresholding (clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79) puts
+    ``sgd_x0_quantile`` -- the per-sample quantile of |x0| -- in front of the step."""
+
+    COEF = (5, torch.float32)
+    NOISE = True
+    EXTRAS = True
+
+    def alloc(self, img):
+        self.z, self.x0 = torch.empty_like(img), torch.empty_like(img)
+        self.rank = _quantile_rank(self.dtp, img[0].numel()) if self.dtp < 1.0 else None
+        self.s_dyn = None if self.rank is None else torch.empty(img.shape[0], device=img.device)
+
+    def draw(self, noise=None, static=True):
+        """this step's z: == torch.randn(shape) (noise_like, util.py:264-267), or the injected one -- copied into ``z``, the
+        buffer a captured launch reads (``static``), or read as it is"""
+        z = self.z
+        if noise is None:
+            z.normal_()
+        elif static:
+            z.copy_(noise)
+        else:
+            z = noise
+        return torch.nn.functional.dropout(z, p=self.noise_dropout) if self.noise_dropout > 0. else z
+
+    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True):
+        lib, ddpm, dyn = self.lib, self.kind == "ddpm", None
+        if self.rank is not None:
+            # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C] (the layout is
+            # told by (b, c), not by the mode: the converted eps of parameterization 'v' is [B, hw, C] with mode 0)
+            B, Cc = self.x0.shape[:2]
+            if (b, c) != (B, Cc):
+                eps, b, c = eps.reshape(B, Cc, hw).permute(0, 2, 1).contiguous(), B, Cc
+            dyn = self.s_dyn
+            L.check(lib.sgd_x0_quantile(0 if ddpm else 1, _ptr(x), _ptr(eps), mode, w, row_dev, b, c, hw, *self.rank,
+                                        _ptr(dyn), st), "sgd_x0_quantile")
+        head = _ptr(x), _ptr(eps), _ptr(self.z if z is None else z), mode, w, row_dev
+        tail = self.clip, _ptr(dyn), b, c, hw, _ptr(x_out), _ptr(self.x0 if want_x0 else None), st
+        if ddpm:
+            L.check(lib.sgd_ddpm_step(*head, *tail), "sgd_ddpm_step")
+        else:
+            L.check(lib.sgd_ddim_step(*head, self.temperature, *tail), "sgd_ddim_step")
+
+
+class _PNDMUpdate(_Update):
+    """``sgd_pndm_step``.  Its state is the Runge-Kutta accumulator, the warm-up start image and the 3-slot eps history; a
+    row is one ``sgd_pndm_row`` (include/sgdm_hip.h), which says which update the launch performs, so ONE captured step
+    serves warm-up and multistep evaluations alike.  No ``z``: the only RNG use per evaluation is the cond-drop mask's
+    ``uniform_``, as in the reference (pndm_sampler.py:176-208); no clipping, no x0."""
+
+    COEF = (8, torch.int32)
+
+    def alloc(self, img):
+        self.acc, self.base = torch.empty_like(img), torch.empty_like(img)
+        self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
+
+    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out):
+        L.check(self.lib.sgd_pndm_step(_ptr(x), _ptr(eps), mode, w, row_dev, _ptr(self.acc), _ptr(self.base),
+                                       _ptr(self.ring), b, c, hw, _ptr(x_out), st), "sgd_pndm_step")
+
+
+class _DPMUpdate(_Update):
+    """``sgd_dpmpp_step``.  A row is one ``sgd_dpmpp_row`` (include/sgdm_hip.h); ``x0``, the clipped data prediction the
+    snapshots log, is also the multistep history the next launch reads.  A trajectory's first row has ``cp == 0``, so what
+    an earlier trajectory left in a cached step's ``x0`` is never read.  No ``z``."""
+
+    COEF = (8, torch.float32)
+
+    def alloc(self, img):
+        self.x0 = torch.empty_like(img)
+
+    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out):
+        L.check(self.lib.sgd_dpmpp_step(_ptr(x), _ptr(eps), mode, w, row_dev, _ptr(self.x0), self.clip, b, c, hw,
+                                        _ptr(x_out), st), "sgd_dpmpp_step")
+
+
 class _GraphedStep:
     """One CFG sampling step -- UNet at 2B (~135 launches) + the fused update -- captured into a hipGraph
     (``torch.cuda.CUDAGraph`` capture of the stream the C-ABI launchers are given), cached on the model per
     (batch, resolution, precision, guidance, sampler, parameterization) and replayed per step.
 
-    Everything a step varies lives in fixed device buffers the captured kernels read: ``img`` (updated in place by
-    ``sgd_*_step_dev``), ``t`` [B], ``coef`` (row of the per-step table), ``z`` and the cond-drop mask.  The RNG draws
-    (``z``, the mask's ``uniform_``) stay OUTSIDE the graph, in the reference's order, so seeded trajectories are the
-    same with and without the graph.  Host work per step: 5 tiny torch ops + one graph launch instead of ~140 ctypes
-    launches -- irrelevant at UNet batch 80 (21 ms of GPU work per step) and the difference between host-bound and
-    device-bound at C1 size (ch=64, 32x32, bs=8).  Reference loops: ddpm_sampler.py:194-238, ddim_plms_sampler.py:302-344.
+    Everything a step varies lives in fixed device buffers the captured kernels read: ``img`` (updated in place), ``t`` [B],
+    ``coef`` (row of the per-step table), the update's ``z`` and state, and the cond-drop mask.  The RNG draws (``z``, the
+    mask's ``uniform_``) stay OUTSIDE the graph, in the reference's order, so seeded trajectories are the same with and
+    without the graph.  Host work per step: 5 tiny torch ops + one graph launch instead of ~140 ctypes launches --
+    irrelevant at UNet batch 80 (21 ms of GPU work per step) and the difference between host-bound and device-bound at C1
+    size (ch=64, 32x32, bs=8).  Reference loops: ddpm_sampler.py:194-238, ddim_plms_sampler.py:302-344.
     """
 
     MAX_PER_ENGINE = 8          # captured steps kept per (model, batch, resolution, precision) engine
-    COEF = (5, torch.float32)   # one row of the trajectory's table
-    NOISE = True                # the update reads a z
 
     @classmethod
-    def get(cls, runner, img, kind, clip, times, tab, temperature=1.0):
+    def get(cls, runner, img, upd, times, tab):
         """the captured step for this (model, batch, resolution, precision, guidance, sampler) -- built on first use and
         kept on the model, so later trajectories of the same configuration only refresh the static input buffers"""
         m, kw = runner.model, runner.kwargs
@@ -208,11 +308,11 @@ class _GraphedStep:
         eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec)
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
         par = "eps" if runner.v is None else ("v", runner.v[0].numel())
-        key = (id(eng), tuple(img.shape), kind, clip, float(temperature), float(kw["cond_scale"]), m._scale_mode(),
+        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, float(kw["cond_scale"]), m._scale_mode(),
                sig(cond), sig(layout), par)
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
-        g = cache.get(key)
-        if g is None:
+        g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
+        if g is None:                                       # the key covers all of ``upd`` that the capture baked in
             live = {id(e) for e in m._engines.values()}
             for k in [k for k in cache if k[0] not in live]:
                 del cache[k]                                # graphs of a replaced engine (parameters re-allocated)
@@ -220,21 +320,20 @@ class _GraphedStep:
             for k in mine[:max(0, len(mine) - (cls.MAX_PER_ENGINE - 1))]:
                 del cache[k]                                # oldest first (dicts keep insertion order): a sweep over
                                                             # guidance weights / temperatures must not grow without bound
-            g = cache[key] = cls(runner, eng, img, kind, clip, temperature)
+            g = cache[key] = cls(runner, eng, img, upd)
         g.begin(img, cond, layout, times, tab, runner.v)
         return g
 
-    def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
+    def __init__(self, runner, eng, img, upd):
         m = runner.model
-        self.m, self.lib, self.kind, self.eng = m, runner.lib, kind, eng
+        self.m, self.upd, self.eng = m, upd, eng
         B, Cc = img.shape[0], img.shape[1]
         hw = int(np.prod(img.shape[2:]))
         dev = img.device
         self.img = torch.empty_like(img)
         self.t = torch.zeros(B, dtype=torch.long, device=dev)
-        self.coef = torch.zeros(self.COEF[0], dtype=self.COEF[1], device=dev)
-        self.z = torch.empty_like(img) if self.NOISE else None
-        self.x0 = torch.empty_like(img)                 # clipped x0 prediction of the step (snapshot steps clone it)
+        self.coef = torch.zeros(upd.COEF[0], dtype=upd.COEF[1], device=dev)
+        upd.alloc(self.img)
         kw = runner.kwargs
         # static copies in exactly the dtypes the boundary kernels read (prepare() must not re-allocate them)
         c0, l0 = kw.get("cond"), kw.get("layout")
@@ -264,19 +363,11 @@ class _GraphedStep:
                 eps = eng.eps_nhwc
                 if self.v is not None:                  # v -> guided eps at this step's time; the update reads it with mode 0
                     eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
-                self._launch_update(st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature)
+                # reads ``eps`` (the UNet's output in the engine, or the converted eps), updates img in place
+                upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
         torch.cuda.current_stream(dev).wait_stream(side)
 
-    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
-        """the update kernel of the captured step (reads ``eps``: the UNet's output in the engine, or the converted eps of
-        parameterization 'v'; updates img in place)"""
-        if kind == "ddpm":
-            L.check(self.lib.sgd_ddpm_step_dev(_ptr(img), _ptr(eps), _ptr(self.z), mode, w, _ptr(self.coef),
-                                               clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st), "sgd_ddpm_step_dev")
-        else:
-            L.check(self.lib.sgd_ddim_step_dev(_ptr(img), _ptr(eps), _ptr(self.z), mode, w, _ptr(self.coef),
-                                               float(temperature), clip, B, Cc, hw, _ptr(img), _ptr(self.x0), st),
-                    "sgd_ddim_step_dev")
+    x0 = property(lambda self: self.upd.x0)
 
     def begin(self, img, cond, layout, times, tab, v=None):
         """start of a trajectory: x_T, the guidance tensors, the trajectory's tables (UNet time and coefficient row per
@@ -298,10 +389,8 @@ class _GraphedStep:
             self.u.uniform_(0, 1)                       # prob_mask_like (openaimodel.py:462-463): same RNG consumption
             torch.lt(self.u, self.p, out=self.mask)
         self.t.copy_(self.ts[i])
-        if noise is not None:
-            self.z.copy_(noise)
-        elif self.NOISE:
-            self.z.normal_()                            # == torch.randn(shape) (noise_like, util.py:264-267)
+        if self.upd.NOISE:
+            self.upd.draw(noise)
         self.coef.copy_(self.tab[i])
         self.graph.replay()
 
@@ -309,97 +398,33 @@ class _GraphedStep:
         return self.img.clone()                         # the static buffer belongs to the cached graph
 
 
-class _GraphedPNDMStep(_GraphedStep):
-    """The captured step of the PNDM sampler: UNet at 2B + ``sgd_pndm_step``.  Its static buffers are the Runge-Kutta
-    accumulator, the warm-up start image and the 3-slot eps history; ``coef`` holds one ``sgd_pndm_row``
-    (include/sgdm_hip.h), which says which update the replay performs, so ONE graph serves warm-up and multistep
-    evaluations alike.  No ``z`` is drawn: the only RNG use per evaluation is the cond-drop mask's ``uniform_``, as in the
-    reference (pndm_sampler.py:176-208)."""
-
-    COEF = (8, torch.int32)
-    NOISE = False
-
-    def __init__(self, runner, eng, img, kind, clip, temperature=1.0):
-        self.acc = torch.empty_like(img)
-        self.base = torch.empty_like(img)
-        self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
-        super().__init__(runner, eng, img, kind, clip, temperature)
-
-    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
-        L.check(self.lib.sgd_pndm_step(_ptr(img), _ptr(eps), mode, w, _ptr(self.coef), _ptr(self.acc),
-                                       _ptr(self.base), _ptr(self.ring), B, Cc, hw, _ptr(img), st), "sgd_pndm_step")
-
-
-class _GraphedDPMStep(_GraphedStep):
-    """The captured step of the DPM-Solver++(2M) sampler: UNet at 2B + ``sgd_dpmpp_step``.  ``coef`` holds one
-    ``sgd_dpmpp_row`` (include/sgdm_hip.h); ``x0``, the clipped data prediction the snapshots log, is also the multistep
-    history the next replay reads.  A trajectory's first row has ``cp == 0``, so what an earlier trajectory left in the
-    cached graph's ``x0`` is never read.  No ``z`` is drawn."""
-
-    COEF = (8, torch.float32)
-    NOISE = False
-
-    def _launch_update(self, st, img, eps, mode, w, B, Cc, hw, kind, clip, temperature):
-        L.check(self.lib.sgd_dpmpp_step(_ptr(img), _ptr(eps), mode, w, _ptr(self.coef), _ptr(self.x0), clip,
-                                        B, Cc, hw, _ptr(img), st), "sgd_dpmpp_step")
-
-
-def _quantile_rank(dtp, count):
-    """(lo, hi, frac) of torch.quantile(., dtp) over `count` fp32 values: rank = q * (count - 1) in the input dtype,
-    linear interpolation between the order statistics floor(rank) and ceil(rank)"""
-    rank = torch.tensor(dtp, dtype=torch.float32) * (count - 1)
-    lo = torch.floor(rank)
-    return int(lo), int(torch.ceil(rank)), float(rank - lo)
-
-
 class _EagerStep:
     """The same step launched kernel by kernel, with the captured step's surface (``step``, ``img``, ``x0``, ``final``).  It
-    covers what the capture leaves out: a generic ``denoise_sample_fn`` (guided NCHW eps), a given eps (PLMS), noise
-    dropout and dynamic thresholding.  RNG order per step as in the reference: the cond-drop ``uniform_`` inside the UNet
-    call, then ``z`` (drawn at eta = 0 too)."""
+    covers what the capture leaves out: a generic ``denoise_sample_fn`` (guided NCHW eps), the ``cond_scale`` 0 / 1
+    shortcuts, ``p0``, ``hip_graph=False``, a given eps (PLMS), noise dropout and dynamic thresholding.  RNG order per step
+    as in the reference: the cond-drop ``uniform_`` inside the UNet call, then ``z`` (drawn at eta = 0 too).  The
+    trajectory's table is uploaded once and a step hands the kernel the address of its row; the image ping-pongs between
+    two buffers (PLMS goes ``back`` to the pre-step one)."""
 
-    def __init__(self, runner, img, kind, clip, times, tab, sk, temperature=1.0):
-        self.runner, self.lib, self.kind, self.clip = runner, runner.lib, kind, clip
-        self.temperature = float(temperature)
+    def __init__(self, runner, img, upd, times, tab):
+        self.runner, self.upd = runner, upd
         B, Cc = img.shape[0], img.shape[1]
         self.dims = B, Cc, int(np.prod(img.shape[2:]))
-        self.img, self.nxt, self.x0 = img, torch.empty_like(img), torch.empty_like(img)
-        assert tab.device.type == "cpu" and tab.dtype == torch.float32       # the kernels take a row as HOST floats
-        self.ts, self.tab = _t_rows(times, B, img.device), tab.contiguous()
-        self.noise_dropout = sk["noise_dropout"]
-        # dynamic thresholding (dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79): per-sample quantile of |x0|
-        self.rank = _quantile_rank(sk["dtp"], Cc * self.dims[2]) if sk.get("dtp", 1) < 1.0 else None
-        self.s_dyn = torch.empty(B, device=img.device)
+        self.img, self.nxt = img, torch.empty_like(img)
+        upd.alloc(img)
+        self.ts, self.tab = _t_rows(times, B, img.device), tab.to(img.device).contiguous()
+        assert tuple(self.tab.shape[1:]) == upd.COEF[:1] and self.tab.dtype == upd.COEF[1]
+        self.row0, self.row_bytes = self.tab.data_ptr(), self.tab.shape[1] * self.tab.element_size()
+
+    x0 = property(lambda self: self.upd.x0)
 
     def step(self, i, noise=None, want_x0=False, eps=None):
         """schedule row i from ``img``; ``eps``: a guided NCHW eps to use instead of evaluating the UNet at ``ts[i]``"""
-        lib, img, (B, Cc, hw) = self.lib, self.img, self.dims
-        coef = C.cast(self.tab[i].data_ptr(), C.POINTER(C.c_float))
+        img, (B, Cc, hw) = self.img, self.dims
         # a guided NCHW eps is "NHWC with one channel" over B*C planes
         e, mode, w, bb, cc = self.runner.eps(img, self.ts[i]) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
-        z = torch.randn(img.shape, device=img.device) if noise is None else noise
-        if self.noise_dropout > 0.:
-            z = torch.nn.functional.dropout(z, p=self.noise_dropout)
-        x0, ddpm = self.x0 if want_x0 else None, self.kind == "ddpm"
-        if self.rank is not None:
-            # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C] (the layout is
-            # told by (bb, cc), not by the mode: the converted eps of parameterization 'v' is [B, hw, C] with mode 0)
-            e4 = e if (bb, cc) == (B, Cc) else e.reshape(B, Cc, hw).permute(0, 2, 1).contiguous()
-            L.check(lib.sgd_x0_quantile(0 if ddpm else 1, _ptr(img), _ptr(e4), mode, w, coef, B, Cc, hw, *self.rank,
-                                        _ptr(self.s_dyn), _stream()), "sgd_x0_quantile")
-            if ddpm:
-                L.check(lib.sgd_ddpm_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, _ptr(self.s_dyn), B, Cc, hw,
-                                              _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddpm_step_dyn")
-            else:
-                L.check(lib.sgd_ddim_step_dyn(_ptr(img), _ptr(e4), _ptr(z), mode, w, coef, self.temperature,
-                                              _ptr(self.s_dyn), B, Cc, hw, _ptr(self.nxt), _ptr(x0), _stream()),
-                        "sgd_ddim_step_dyn")
-        elif ddpm:
-            L.check(lib.sgd_ddpm_step(_ptr(img), _ptr(e), _ptr(z), mode, w, coef, self.clip, bb, cc, hw,
-                                      _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddpm_step")
-        else:
-            L.check(lib.sgd_ddim_step(_ptr(img), _ptr(e), _ptr(z), mode, w, coef, self.temperature, self.clip,
-                                      bb, cc, hw, _ptr(self.nxt), _ptr(x0), _stream()), "sgd_ddim_step")
+        opts = dict(z=self.upd.draw(noise, static=False), want_x0=want_x0) if self.upd.NOISE else {}
+        self.upd.launch(_stream(), img, e, mode, w, bb, cc, hw, self.row0 + i * self.row_bytes, self.nxt, **opts)
         self.img, self.nxt = self.nxt, img
 
     def back(self):
@@ -410,61 +435,15 @@ class _EagerStep:
         return self.img
 
 
-class _EagerPNDMStep:
-    """``_GraphedPNDMStep`` launched kernel by kernel; a new image per evaluation, as the reference's step returns"""
-
-    def __init__(self, runner, img, times, tab):
-        self.runner, self.img = runner, img
-        self.hw = int(np.prod(img.shape[2:]))
-        self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
-        self.acc, self.base = torch.empty_like(img), torch.empty_like(img)
-        self.ring = torch.empty((3,) + tuple(img.shape), device=img.device)
-
-    def step(self, i):
-        eps, mode, w, bb, cc = self.runner.eps(self.img, self.ts[i])
-        nxt = torch.empty_like(self.img)
-        L.check(self.runner.lib.sgd_pndm_step(_ptr(self.img), _ptr(eps), mode, w, _ptr(self.tab[i]), _ptr(self.acc),
-                                              _ptr(self.base), _ptr(self.ring), bb, cc, self.hw, _ptr(nxt), _stream()),
-                "sgd_pndm_step")
-        self.img = nxt
-
-    def final(self):
-        return self.img
-
-
-class _EagerDPMStep:
-    """``_GraphedDPMStep`` launched kernel by kernel (generic ``denoise_sample_fn``, the ``cond_scale`` 0 / 1 shortcuts,
-    ``p0``, ``hip_graph=False``); the image ping-pongs between two buffers"""
-
-    def __init__(self, runner, img, clip, times, tab):
-        self.runner, self.img, self.clip = runner, img, clip
-        self.hw = int(np.prod(img.shape[2:]))
-        self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
-        self.nxt, self.x0 = torch.empty_like(img), torch.empty_like(img)
-
-    def step(self, i):
-        eps, mode, w, bb, cc = self.runner.eps(self.img, self.ts[i])
-        L.check(self.runner.lib.sgd_dpmpp_step(_ptr(self.img), _ptr(eps), mode, w, _ptr(self.tab[i]), _ptr(self.x0),
-                                               self.clip, bb, cc, self.hw, _ptr(self.nxt), _stream()), "sgd_dpmpp_step")
-        self.img, self.nxt = self.nxt, self.img
-
-    def final(self):
-        return self.img
-
-
-def _graph_ok(runner, sk):
-    """the captured step covers the common case only: fused CFG evaluation on the drop-in UNet, no noise dropout, no
-    dynamic thresholding; ``hip_graph=False`` in the sampling kwargs (or SGDM_HIP_GRAPH=0) turns it off"""
-    if not sk.get("hip_graph", True) or os.environ.get("SGDM_HIP_GRAPH", "1") == "0":
-        return False
-    return runner.fused_cfg() and sk.get("noise_dropout", 0) == 0 and sk.get("dtp", 1) >= 1.0
-
-
-def _sampler_step(runner, sk, img, kind, clip, times, tab, temperature=1.0):
-    """the step object a DDPM / DDIM loop walks its schedule with: captured where ``_graph_ok`` allows, else eager"""
-    if _graph_ok(runner, sk):
-        return _GraphedStep.get(runner, img, kind, clip, times, tab, temperature)
-    return _EagerStep(runner, img, kind, clip, times, tab, sk, temperature)
+def _sampler_step(runner, sk, img, upd, times, tab, capture=True):
+    """the step object a sampler's loop walks its schedule with.  Captured in the common case: fused CFG evaluation on the
+    drop-in UNet and nothing asked of the update that only the eager step runs (noise dropout, dynamic thresholding -- an
+    update that does not honour them never sees them); ``hip_graph=False`` in the sampling kwargs (or SGDM_HIP_GRAPH=0) and
+    ``capture=False`` (PLMS: the eps is the caller's) turn the capture off"""
+    on = capture and sk.get("hip_graph", True) and os.environ.get("SGDM_HIP_GRAPH", "1") != "0"
+    if on and runner.fused_cfg() and upd.noise_dropout == 0 and upd.dtp >= 1.0:
+        return _GraphedStep.get(runner, img, upd, times, tab)
+    return _EagerStep(runner, img, upd, times, tab)
 
 
 class _Snapshots:
@@ -608,7 +587,7 @@ class Schedule_DDPM(nn.Module):
             temperature = [float(temperature)] * timesteps
         snaps = _Snapshots(timesteps, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        stepper = _sampler_step(runner, sk, img, "ddpm", 1 if sk["clip_denoised"] else 0, range(timesteps),
+        stepper = _sampler_step(runner, sk, img, _DDUpdate("ddpm", sk, 1 if sk["clip_denoised"] else 0), range(timesteps),
                                 self.step_table(temperature))
         order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
         for i in (reversed(range(0, timesteps)) if order is None else order):
@@ -664,8 +643,8 @@ class DDIMSampler(object):
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        stepper = _EagerStep(runner, img, "ddim", 1 if sk["clip_denoised"] else 0, self.ddim_timesteps, self.step_table, sk,
-                             float(sk["temperature"]))
+        upd = _DDUpdate("ddim", sk, 1 if sk["clip_denoised"] else 0, sk["temperature"])
+        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, self.step_table, capture=False)
         B, Cc, hw = stepper.dims
         draws = iter(range(total + 1))
 
@@ -750,8 +729,8 @@ class DDIMSampler(object):
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk, host=True)
-        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw, sk, dev), sk, img, "ddim", 1 if sk["clip_denoised"] else 0,
-                                self.ddim_timesteps, self.step_table, float(sk["temperature"]))
+        upd = _DDUpdate("ddim", sk, 1 if sk["clip_denoised"] else 0, sk["temperature"])
+        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw, sk, dev), sk, img, upd, self.ddim_timesteps, self.step_table)
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
         for index in (reversed(range(total)) if visit is None else map(int, visit)):
@@ -843,11 +822,7 @@ class PNDM_Sampler(object):
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        # PNDM ignores dtp and noise_dropout: only the model / guidance conditions of the captured step apply
-        if _graph_ok(runner, dict(sk, noise_dropout=0, dtp=1)):
-            stepper = _GraphedPNDMStep.get(runner, img, "pndm", 0, times, tab)
-        else:
-            stepper = _EagerPNDMStep(runner, img, times, tab)
+        stepper = _sampler_step(runner, sk, img, _PNDMUpdate("pndm", sk, 0), times, tab)
         for k in range(len(times)):
             stepper.step(k)
         img = stepper.final()
@@ -933,14 +908,9 @@ class DPMSolverSampler(object):
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        clip = 1 if sk["clip_denoised"] else 0
         total = len(ts)
         snaps = _Snapshots(total, sk)
-        # noise dropout is ignored (no noise is drawn): only the model / guidance conditions of the captured step apply
-        if _graph_ok(runner, dict(sk, noise_dropout=0)):
-            stepper = _GraphedDPMStep.get(runner, img, "dpmsolver", clip, ts, tab)
-        else:
-            stepper = _EagerDPMStep(runner, img, clip, ts, tab)
+        stepper = _sampler_step(runner, sk, img, _DPMUpdate("dpmsolver", sk, 1 if sk["clip_denoised"] else 0), ts, tab)
         for index in reversed(range(total)):
             stepper.step(index)
             if index in snaps.rows:

@@ -21,7 +21,7 @@ def test_enum_values_agree_between_header_and_binding():
     enum, txt = _header_enum()
     assert enum == L.PREC_BY_NAME
     assert enum["f16"] == 3 and enum["bf16"] == 4
-    assert int(re.search(r"#define SGD_ABI_VERSION (\d+)", txt).group(1)) == L.ABI_VERSION == 24
+    assert int(re.search(r"#define SGD_ABI_VERSION (\d+)", txt).group(1)) == L.ABI_VERSION == 25
     assert set(L.INFERENCE_ONLY) == {"f16", "bf16"}
 
 

@@ -206,12 +206,12 @@ def test_first_order_on_uniform_times_is_ddim(n):
 def _count_replays(monkeypatch):
     from sgdm_amd import diffusion as Dm
     count = [0]
-    orig = Dm._GraphedDPMStep.step
+    orig = Dm._GraphedStep.step
 
     def step(self, *a, **k):
         count[0] += 1
         return orig(self, *a, **k)
-    monkeypatch.setattr(Dm._GraphedDPMStep, "step", step)
+    monkeypatch.setattr(Dm._GraphedStep, "step", step)
     return count
 
 

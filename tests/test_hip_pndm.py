@@ -93,12 +93,12 @@ def test_free_running_vs_reference():
 def _count_replays(monkeypatch):
     from sgdm_amd import diffusion as Dm
     count = [0]
-    orig = Dm._GraphedPNDMStep.step
+    orig = Dm._GraphedStep.step
 
     def step(self, *a, **k):
         count[0] += 1
         return orig(self, *a, **k)
-    monkeypatch.setattr(Dm._GraphedPNDMStep, "step", step)
+    monkeypatch.setattr(Dm._GraphedStep, "step", step)
     return count
 
 

@@ -83,13 +83,13 @@ def test_ddim_teacher_forced_steps_vs_oracle():
         x_ref, x0_ref = D.ddim_step(tabs, index, x, eps_ref, z[i])
         xd = x.cuda()
         eps, mode, w, bb, cc = runner.eps(xd, ts.cuda())
-        coef = (C.c_float * 4)(float(ds.ddim_sqrt_one_minus_alphas[index]), float(ds.ddim_alphas[index]),
-                               float(ds.ddim_alphas_prev[index]), float(ds.ddim_sigmas[index]))
+        coef = torch.tensor([float(ds.ddim_sqrt_one_minus_alphas[index]), float(ds.ddim_alphas[index]),
+                             float(ds.ddim_alphas_prev[index]), float(ds.ddim_sigmas[index]), 0.0], dtype=torch.float32).cuda()
         out, x0 = torch.empty_like(xd), torch.empty_like(xd)
         zd = z[i].cuda()
         L.check(L.load().sgd_ddim_step(C.c_void_p(xd.data_ptr()), C.c_void_p(eps.data_ptr()), C.c_void_p(zd.data_ptr()),
-                                       mode, w, coef, 1.0, 1, bb, cc, 256, C.c_void_p(out.data_ptr()),
-                                       C.c_void_p(x0.data_ptr()), torch.cuda.current_stream().cuda_stream), "ddim")
+                                       mode, w, C.c_void_p(coef.data_ptr()), 1.0, 1, None, bb, cc, 256,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(x0.data_ptr()), torch.cuda.current_stream().cuda_stream), "ddim")
         assert rel_l2(out.cpu(), x_ref) < 1e-4, index           # north_star: 1e-4 per evaluation
         assert rel_l2(x0.cpu(), x0_ref) < 1e-4, index
         x = x_ref                                                # teacher forcing
@@ -306,9 +306,10 @@ def test_x0_quantile_kernel_matches_torch_quantile(kind, dtp):
     want = torch.quantile(x0.reshape(B, -1).abs(), dtp, dim=-1).clamp(min=1.0)
     lo, hi, frac = _quantile_rank(dtp, Cc * hw)
     s = torch.empty(B, device="cuda")
-    xd = x.cuda()
-    L.check(lib.sgd_x0_quantile(kind, C.c_void_p(xd.data_ptr()), C.c_void_p(eps.data_ptr()), 1, w, coef, B, Cc, hw, lo, hi,
-                                frac, C.c_void_p(s.data_ptr()), torch.cuda.current_stream().cuda_stream), "quantile")
+    xd, coef_d = x.cuda(), torch.tensor(list(coef), dtype=torch.float32).cuda()       # the same five floats, as a device row
+    L.check(lib.sgd_x0_quantile(kind, C.c_void_p(xd.data_ptr()), C.c_void_p(eps.data_ptr()), 1, w,
+                                C.c_void_p(coef_d.data_ptr()), B, Cc, hw, lo, hi, frac, C.c_void_p(s.data_ptr()),
+                                torch.cuda.current_stream().cuda_stream), "quantile")
     assert max_rel(s.cpu(), want) < 2e-6
 
 
@@ -448,3 +449,76 @@ def test_dynamic_thresholding_trajectories_vs_reference():
     diff = (samples.cpu().int() - torch.from_numpy(v["dtp_native.samples_u8"]).int()).abs()
     assert diff.max() <= 1 and (diff != 0).float().mean() < 1e-2
     assert rel_l2(inter["x_inter"].cpu(), v["dtp_native.x_inter"]) < 1e-3
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# sgd_ddpm_step / sgd_ddim_step, the entry points themselves: 2 * 3 * 65 = 390 elements, so the second of two blocks is
+# ragged, and an odd hw, so the (n, cc, p) split of the flat index matters; eps at 2b rows for the two guided modes
+
+_SB, _SC, _SHW = 2, 3, 65
+_ROWS = dict(ddpm=[1.25, 0.75, 0.3, 0.6, 0.2], ddim=[0.6, 0.64, 0.8, 0.1, 0.0])     # x0 leaves [-1, 1] for most elements
+
+
+def _step_inputs(mode):
+    g = torch.Generator().manual_seed(31 + mode)
+    x, z = torch.randn(_SB, _SC, _SHW, generator=g).cuda(), torch.randn(_SB, _SC, _SHW, generator=g).cuda()
+    return x, torch.randn((2 if mode else 1) * _SB, _SHW, _SC, generator=g).cuda(), z
+
+
+def _step_call(kind, x, eps, z, mode, out, x0, clip=1, dyn=None, over=None):
+    """one launch; ``over`` replaces arguments by their C names (None: NULL).  Returns the entry point's status."""
+    from sgdm_amd import _lib as L
+    from sgdm_amd.unet import _ptr
+    row = torch.tensor(_ROWS[kind], dtype=torch.float32).cuda()
+    a = dict(x=_ptr(x), eps=_ptr(eps), z=_ptr(z), mode=mode, w=1.5, coef=_ptr(row))
+    if kind == "ddim":
+        a["temperature"] = 0.9
+    a.update(clip=clip, dyn=_ptr(dyn), b=_SB, c=_SC, hw=_SHW, out=_ptr(out), x0=_ptr(x0), st=torch.cuda.current_stream().cuda_stream)
+    a.update({k: (_ptr(None) if v is None else v) for k, v in (over or {}).items()})
+    rc = getattr(L.load(), f"sgd_{kind}_step")(*a.values())                      # (keyword order is the C argument order)
+    torch.cuda.synchronize()                                                    # `row` lives until the launch has run
+    return rc
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("kind", ["ddpm", "ddim"])
+def test_step_in_place_equals_out_of_place(kind, mode):
+    x, eps, z = _step_inputs(mode)
+    out, x0 = torch.empty_like(x), torch.empty_like(x)
+    assert _step_call(kind, x, eps, z, mode, out, x0) == 0
+    xi, x0i = x.clone(), torch.empty_like(x)
+    assert _step_call(kind, xi, eps, z, mode, xi, x0i) == 0                     # x_out == x
+    assert torch.equal(xi, out) and torch.equal(x0i, x0)
+    assert not torch.equal(out, x) and float(x0.abs().max()) == 1.0            # it did step, and the clip was active
+    bare, xb = torch.empty_like(x), x.clone()
+    assert _step_call(kind, x, eps, z, mode, bare, None) == 0                   # x0_out = NULL: the same image
+    assert _step_call(kind, xb, eps, z, mode, xb, None) == 0
+    assert torch.equal(bare, out) and torch.equal(xb, out)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("kind", ["ddpm", "ddim"])
+def test_step_dyn_s_of_one_is_the_static_clip(kind, mode):
+    """clamp(x0, -1, 1) / 1 is exact: dyn_s == 1.0f everywhere must give the bytes of dyn_s = NULL, clip = 1"""
+    x, eps, z = _step_inputs(mode)
+    out, x0 = torch.empty_like(x), torch.empty_like(x)
+    assert _step_call(kind, x, eps, z, mode, out, x0, clip=1, dyn=None) == 0
+    for clip in (0, 1):                                                         # clip is ignored once dyn_s is given
+        o1, p1 = torch.empty_like(x), torch.empty_like(x)
+        assert _step_call(kind, x, eps, z, mode, o1, p1, clip=clip, dyn=torch.ones(_SB, device="cuda")) == 0
+        assert torch.equal(o1, out) and torch.equal(p1, x0)
+    o2, p2 = torch.empty_like(x), torch.empty_like(x)
+    assert _step_call(kind, x, eps, z, mode, o2, p2, dyn=torch.tensor([2.0, 1.0]).cuda()) == 0
+    assert not torch.equal(o2[0], out[0]) and not torch.equal(p2[0], x0[0])   # the scale is per sample: sample 0 moved,
+    assert torch.equal(o2[1], out[1]) and torch.equal(p2[1], x0[1])           # sample 1 did not
+
+
+@pytest.mark.parametrize("kind", ["ddpm", "ddim"])
+def test_step_entry_point_refuses_bad_arguments(kind):
+    x, eps, z = _step_inputs(1)
+    out = torch.full_like(x, float("nan"))
+    x0 = torch.full_like(x, float("nan"))
+    for bad in (dict(coef=None), dict(x=None), dict(eps=None), dict(z=None), dict(out=None), dict(b=0), dict(b=-1), dict(c=0),
+                dict(c=-3), dict(hw=0), dict(hw=-65), dict(mode=3)):
+        assert _step_call(kind, x, eps, z, 1, out, x0, over=bad) == 1, bad          # SGD_ERR_ARG ...
+    assert torch.isnan(out).all() and torch.isnan(x0).all()                     # ... and nothing was launched

@@ -77,6 +77,16 @@ def main():
         for graph in (False, True):
             run(f"{name} native parameterization=x0 {'graph' if graph else 'eager'}", x0p, "native",
                 skw(1000, hip_graph=graph), dkw, **short)
+        # parameterization 'v': the v -> eps pass in front of the update, eager and captured (a direct sampler call names the
+        # parameterization and the schedule's two tables in its kwargs)
+        vp = LatentDiffusion(device="cuda", **dict(bench.MODEL_PARAMS, parameterization="v"))
+        vp.set_denoise_fn(m.forward, m.forward_with_cond_scale)
+        vk = dict(parameterization="v", sqrt_alphas_cumprod=vp.sampler.sqrt_alphas_cumprod,
+                  sqrt_one_minus_alphas_cumprod=vp.sampler.sqrt_one_minus_alphas_cumprod)
+        for graph in (False, True):
+            for method in ("ddim", "dpmsolver"):
+                run(f"{name} {method}-10 parameterization=v {'graph' if graph else 'eager'}", vp, method,
+                    skw(10, hip_graph=graph, **vk), dkw)
         # a plain callable: the generic path (guided NCHW eps from the function, cfg_mode 0), never captured
         plain = LatentDiffusion(device="cuda", **bench.MODEL_PARAMS)
         plain.set_denoise_fn(m.forward, lambda x, t, **kw: m.forward_with_cond_scale(x, t, **kw))
