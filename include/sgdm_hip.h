@@ -422,6 +422,22 @@ int sgd_dpmpp_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, floa
  * (ABI unchanged at 24). */
 int sgd_v_to_eps(const float* x, const float* v_out, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                  int32_t cfg_mode, float w, int32_t b, int32_t c, int32_t hw, float* eps_out, void* stream);
+/* Guidance pass (sampling kwargs cfg_interval / cfg_rescale, sgdm_amd/diffusion.py; no counterpart in the reference): the
+ * guided network output, formed BEFORE the update instead of inside it, with the weight read from DEVICE memory -- no
+ * by-value argument changes between steps, so one captured step serves a whole trajectory and any per-step weight schedule --
+ * and optionally rescaled per sample (CFG rescale, Lin et al. 2023, section 3.4):
+ *   g = guided(out) with w = *w_dev          (cfg_mode 1 | 2 above, each product rounded before it is added)
+ *   rescale == 0: guided_out = g             (element-wise)
+ *   rescale  > 0, per sample n over its c*hw elements:
+ *     s_pos = std(out_cond[n]), s_g = std(g[n])       unbiased (divide by c*hw - 1) like torch.std; each as the mean first,
+ *                                                      then the sum of centred squares, accumulated in fp32
+ *     f = s_g > 0 ? s_pos / s_g : 1   (f = 1 when c*hw == 1);   k = rescale * f + (1 - rescale);   guided_out[n] = k * g[n]
+ * out is [2b, hw, c] ([cond ; uncond]), guided_out is [b, hw, c]: what follows (sgd_v_to_eps, the update kernels,
+ * sgd_x0_quantile) reads it with cfg_mode = 0.  rescale is in [0, 1].  One workgroup per sample when rescale > 0; the
+ * reductions are wave shuffles, then LDS, in a fixed order without atomics: results are identical from run to run and
+ * between a captured and an eager launch.  guided_out must not alias out.  Additive entry (ABI unchanged at 25). */
+int sgd_cfg_guide(const float* out /* [2b, hw, c] */, int32_t cfg_mode /* 1 | 2 */, const float* w_dev /* DEVICE float[1] */,
+                  float rescale, int32_t b, int32_t c, int32_t hw, float* guided_out /* [b, hw, c] */, void* stream);
 /* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s

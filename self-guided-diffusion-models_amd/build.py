@@ -35,6 +35,8 @@ FILE_FLAGS["pndm.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["dpm.hip"] = ["-ffp-contract=off"]
 # vpred.hip: the same -- the v target and the v -> eps change of variables, product by product
 FILE_FLAGS["vpred.hip"] = ["-ffp-contract=off"]
+# guide.hip: the same -- the guided forms of the guidance pass (sgd_cfg_guide), product by product
+FILE_FLAGS["guide.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

@@ -9,6 +9,10 @@ Mirrors (reference, /root/reference):
 Without a counterpart there: DPMSolverSampler ('dpmsolver', DPM-Solver++(2M), include/sgdm_hip.h: sgd_dpmpp_step) and
 parameterization='v' (Salimans & Ho 2022; include/sgdm_hip.h: sgd_q_sample_v, sgd_v_to_eps): the network output read as
 v is changed to a guided eps right after the UNet evaluation (``_StepRunner.v_to_eps``), every update kernel runs unchanged.
+Also without a counterpart: the guidance schedule, sampling kwargs ``cfg_interval`` = (t_lo, t_hi) (Kynkaanniemi et al. 2024:
+guidance only on evaluations whose time lies in the interval, the others ONE evaluation at B) and ``cfg_rescale`` = phi (Lin et
+al. 2023, section 3.4), honoured by all five samplers: ``cfg_options`` / ``cfg_schedule`` (host), ``_StepRunner.guide``
+(include/sgdm_hip.h: sgd_cfg_guide) between the UNet and everything that reads its output, with mode 0 from there on.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -107,14 +111,51 @@ def _v_tables(sk, dev):
     return tuple(a.detach().to(dev, torch.float32).contiguous() for a in (sa, s1))
 
 
+def cfg_options(sk, fused=True):
+    """(cfg_rescale, cfg_interval) of the sampling kwargs: phi in [0, 1] (0: off) and ``(t_lo, t_hi)`` in training timesteps,
+    inclusive (None: guidance on every evaluation).  ValueError for a value out of range and, with an option set, for a step
+    that is not the fused-CFG one (``fused``: _StepRunner.fused_cfg()) -- the guide pass works on the two halves of the doubled
+    evaluation.  Pure host code: no device, no library."""
+    sk = sk or {}
+    phi, iv = sk.get("cfg_rescale", 0), sk.get("cfg_interval")
+    if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:       # (NaN fails the comparison)
+        raise ValueError(f"cfg_rescale={phi!r}: a number in [0, 1]")
+    if iv is not None:
+        ok = isinstance(iv, (tuple, list)) and len(iv) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in iv)
+        if not ok or iv[0] > iv[1]:
+            raise ValueError(f"cfg_interval={iv!r}: (t_lo, t_hi), two ints in training timesteps with t_lo <= t_hi")
+        iv = (int(iv[0]), int(iv[1]))
+    if (phi > 0 or iv is not None) and not fused:
+        raise ValueError("cfg_rescale / cfg_interval need the fused-CFG step: the drop-in UNet's forward_with_cond_scale, a "
+                         "numeric cond_scale that is not its single-evaluation 0 / 1 shortcut, and no p0")
+    return float(phi), iv
+
+
+def cfg_schedule(times, cond_scale, scale_mode, interval=None):
+    """per UNet EVALUATION of a trajectory (``times``: its time argument, one entry per evaluation -- PNDM's list repeats
+    times): (guided, weight).  An evaluation is guided when ``t_lo <= t <= t_hi`` (``interval`` None: always) and then has
+    weight ``cond_scale``; the others take the conditional prediction alone, which is weight 1 of the imagen form
+    (``scale_mode`` 1, _scale_mode()) and weight 0 of the cfg form (2).  Pure host code."""
+    if scale_mode not in (1, 2):
+        raise ValueError(f"scale_mode={scale_mode!r} (1: imagen, 2: cfg)")
+    off = 1.0 if scale_mode == 1 else 0.0
+    guided = [interval is None or interval[0] <= int(t) <= interval[1] for t in times]
+    return guided, [float(cond_scale) if g else off for g in guided]
+
+
 class _StepRunner:
     """one sampling step = UNet(2B) + one fused update kernel (+ the v -> eps pass between them when ``sk`` says
-    parameterization='v')"""
+    parameterization='v').  With ``cfg_rescale`` / ``cfg_interval`` in ``sk`` (``scheduled``) a guided evaluation puts the
+    guide pass (sgd_cfg_guide) behind the UNet and everything after it reads the guided buffer with mode 0; an evaluation
+    outside the interval is ONE UNet evaluation at B, nothing dropped"""
 
     def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
         self.fn = denoise_sample_fn
         self.kwargs = dict(kwargs)
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
+        self.rescale, self.interval = cfg_options(sk, self.fused_cfg())        # refused before anything is loaded or launched
+        self.scheduled = self.rescale > 0 or self.interval is not None
         self.lib = L.load()
         self._drop = {}
         self.v = _v_tables(sk, dev)
@@ -128,6 +169,10 @@ class _StepRunner:
         fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else True
         return not (fast_int and w in (0, 1))
 
+    def schedule(self, times):
+        """(guided flag, weight) per evaluation of a scheduled trajectory (cfg_schedule)"""
+        return cfg_schedule(times, self.kwargs["cond_scale"], self.model._scale_mode(), self.interval)
+
     def drop_mask(self, B, dev):
         """(whether the model reads a cond-drop mask at all, drop probabilities [2B] of the doubled batch: the conditional
         half never, the unconditional half always)"""
@@ -137,19 +182,43 @@ class _StepRunner:
             self._drop[B, dev] = has_mask, torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), 1.0, device=dev)))
         return self._drop[B, dev]
 
-    def eps(self, x, t):
-        """returns (eps tensor/engine buffer, cfg_mode, w, b, c) describing how the step kernel reads it"""
+    def cond_only_mask(self):
+        """whether the model's own single evaluation, ``forward(cond_drop_prob=p0)``, draws a (B-long, all-false) cond-drop
+        mask: a cond-only evaluation consumes the RNG like it (openaimodel.py:861-956, openaimodel_ca.py:879-1033)"""
+        m = self.model
+        if m.KIND == "unetca_fast":
+            return m.cond_token_num > 0 or m.condition_method == "layout"
+        return m.cond_dim > 0
+
+    def guide(self, out, mode, w_dev, B, Cc, hw, g, st):
+        """the guide pass: ``out`` [2B, hw, C] -> ``g`` [B, hw, C], weight from the device float ``w_dev``"""
+        L.check(self.lib.sgd_cfg_guide(_ptr(out), mode, _ptr(w_dev), self.rescale, B, Cc, hw, _ptr(g), st), "sgd_cfg_guide")
+        return g
+
+    def eps(self, x, t, guided=True, w_dev=None):
+        """returns (eps tensor/engine buffer, cfg_mode, w, b, c) describing how the step kernel reads it.  A scheduled
+        trajectory's step object says whether this evaluation is ``guided`` and hands over its weight as a device float"""
         B, Cc = x.shape[0], x.shape[1]
         m = self.model
         if self.fused_cfg():
-            has_mask, p = self.drop_mask(B, x.device)
-            mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-            eng = m._run(x, t, self.kwargs.get("cond"), self.kwargs.get("layout"), mask, 2 * B)
-            mode, w = m._scale_mode(), float(self.kwargs["cond_scale"])
+            kw = self.kwargs
+            if self.scheduled and not guided:
+                # the conditional prediction alone: one evaluation at B, RNG consumed as forward(cond_drop_prob=p0) does
+                mask = m._draw_mask(B, 0.0, x.device) if self.cond_only_mask() else None
+                eng, mode, w = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B), 0, 0.0
+                out = eng.eps_nhwc
+            else:
+                has_mask, p = self.drop_mask(B, x.device)
+                mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
+                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B)
+                out, mode, w = eng.eps_nhwc, m._scale_mode(), float(kw["cond_scale"])
+                if self.scheduled:
+                    g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
+                    out, mode, w = self.guide(out, mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), 0, 0.0
             if self.v is None:
-                return eng.eps_nhwc, mode, w, B, Cc
-            out = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
-            return self.v_to_eps(x, eng.eps_nhwc, t, mode, w, B, Cc, out, _stream()), 0, 0.0, B, Cc
+                return out, mode, w, B, Cc
+            e = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
+            return self.v_to_eps(x, out, t, mode, w, B, Cc, e, _stream()), 0, 0.0, B, Cc
         e = self.fn(x, t, **self.kwargs).contiguous()       # generic path: guided output, NCHW
         if self.v is not None:
             # B*C one-channel planes, one time per plane
@@ -293,6 +362,12 @@ class _GraphedStep:
     without the graph.  Host work per step: 5 tiny torch ops + one graph launch instead of ~140 ctypes launches --
     irrelevant at UNet batch 80 (21 ms of GPU work per step) and the difference between host-bound and device-bound at C1
     size (ch=64, 32x32, bs=8).  Reference loops: ddpm_sampler.py:194-238, ddim_plms_sampler.py:302-344.
+
+    A scheduled step (sampling kwargs cfg_rescale / cfg_interval) captures the guide pass behind the UNet and reads the
+    guidance weight from a one-float device buffer, ``w``, refreshed per step like ``coef``: the weight and the interval's
+    bounds are data, not part of the capture.  With an interval requested the step holds TWO graphs over the same static
+    buffers and the same update object: ``graph`` (2B engine, guide pass) and ``graph1`` (the engine at B, conditional
+    prediction alone); ``step`` replays one or the other by the host table ``begin`` built, and counts them in ``replays``.
     """
 
     MAX_PER_ENGINE = 8          # captured steps kept per (model, batch, resolution, precision) engine
@@ -308,8 +383,11 @@ class _GraphedStep:
         eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec)
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
         par = "eps" if runner.v is None else ("v", runner.v[0].numel())
-        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, float(kw["cond_scale"]), m._scale_mode(),
-               sig(cond), sig(layout), par)
+        # a scheduled step reads its weight from the device: a sweep over weights or intervals reuses one capture (a pair
+        # of graphs, when an interval is requested, is one entry)
+        w = None if runner.scheduled else float(kw["cond_scale"])
+        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, m._scale_mode(), sig(cond), sig(layout), par,
+               (runner.rescale, runner.interval is not None))
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
         if g is None:                                       # the key covers all of ``upd`` that the capture baked in
@@ -321,7 +399,7 @@ class _GraphedStep:
                 del cache[k]                                # oldest first (dicts keep insertion order): a sweep over
                                                             # guidance weights / temperatures must not grow without bound
             g = cache[key] = cls(runner, eng, img, upd)
-        g.begin(img, cond, layout, times, tab, runner.v)
+        g.begin(img, cond, layout, times, tab, runner.v, runner)
         return g
 
     def __init__(self, runner, eng, img, upd):
@@ -350,29 +428,66 @@ class _GraphedStep:
         # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
         self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
         self.veps = None if runner.v is None else torch.empty((B, hw, Cc), device=dev)
+        # scheduled guidance: this step's weight and the guided output
+        self.scheduled = runner.scheduled
+        self.w = torch.zeros(1, device=dev) if self.scheduled else None
+        self.g = torch.empty((B, hw, Cc), device=dev) if self.scheduled else None
+        self.flags = self.wtab = None
+        self.replays = dict(guided=0, cond=0)
+
+        def tail(st, eps, mode, w):
+            if self.v is not None:                      # v -> guided eps at this step's time; the update reads it with mode 0
+                eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
+            # reads ``eps`` (the UNet's output in the engine, the guided buffer or the converted eps), updates img in place
+            upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
+
+        def guided_step(st):
+            eng.launch(st)
+            if self.scheduled:
+                return tail(st, runner.guide(eng.eps_nhwc, mode, self.w, B, Cc, hw, self.g, st), 0, 0.0)
+            tail(st, eng.eps_nhwc, mode, w)
+
+        self.graph = self._capture(eng, guided_step, dev)
+        self.eng1 = self.graph1 = self.u1 = None
+        if runner.interval is not None:
+            # the conditional prediction alone: the engine at B over the same img / t / cond / layout; its mask stays all-false
+            # (``u1`` is only drawn into, to consume the RNG like the model's own single evaluation)
+            eng1 = self.eng1 = m._engine(B, img.shape[2], img.shape[3], eng.prec)
+            self.u1 = torch.zeros(B, device=dev) if runner.cond_only_mask() else None
+            self.mask1 = torch.zeros(B, dtype=torch.bool, device=dev) if runner.cond_only_mask() else None
+            eng1.prepare(img, self.t, self.cond, self.layout, self.mask1)
+            self._inputs1 = eng1._keep_inputs
+
+            def cond_step(st):
+                eng1.launch(st)
+                tail(st, eng1.eps_nhwc, 0, 0.0)
+
+            self.graph1 = self._capture(eng1, cond_step, dev)
+
+    @staticmethod
+    def _capture(eng, body, dev):
+        """``body(stream)`` captured on a side stream into a graph of its own"""
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             if not getattr(eng, "ran", False):
                 eng.launch(side.cuda_stream)            # one-time function attributes are set outside the capture
             side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=side):
-                st = torch.cuda.current_stream(dev).cuda_stream
-                eng.launch(st)
-                eps = eng.eps_nhwc
-                if self.v is not None:                  # v -> guided eps at this step's time; the update reads it with mode 0
-                    eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
-                # reads ``eps`` (the UNet's output in the engine, or the converted eps), updates img in place
-                upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                body(torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.current_stream(dev).wait_stream(side)
+        return graph
 
     x0 = property(lambda self: self.upd.x0)
 
-    def begin(self, img, cond, layout, times, tab, v=None):
+    def begin(self, img, cond, layout, times, tab, v=None, runner=None):
         """start of a trajectory: x_T, the guidance tensors, the trajectory's tables (UNet time and coefficient row per
-        schedule row) and, for parameterization 'v', the two schedule tables into device buffers; packed weights re-checked"""
+        schedule row; scheduled: whether each evaluation is guided, and its weight) and, for parameterization 'v', the two
+        schedule tables into device buffers; packed weights re-checked"""
         self.eng.refresh(torch.cuda.current_stream().cuda_stream)
+        if self.eng1 is not None:
+            self.eng1.refresh(torch.cuda.current_stream().cuda_stream)
         self.img.copy_(img)
         if self.cond is not None:
             self.cond.copy_(cond)
@@ -382,17 +497,28 @@ class _GraphedStep:
             for dst, src in zip(self.v, v):
                 dst.copy_(src)
         self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
+        if self.scheduled:
+            self.flags, ws = runner.schedule(times)
+            self.wtab = torch.tensor(ws, dtype=torch.float32, device=img.device)
+        self.replays = dict(guided=0, cond=0)
 
     def step(self, i, noise=None, want_x0=True):
         """schedule row i; draws the mask uniform and z like the eager step (``x0`` is written on every replay)"""
-        if self.has_mask:
+        guided = self.flags is None or self.flags[i]
+        if not guided:
+            if self.u1 is not None:
+                self.u1.uniform_(0, 1)                  # the B-long draw of forward(cond_drop_prob=p0); nothing is dropped
+        elif self.has_mask:
             self.u.uniform_(0, 1)                       # prob_mask_like (openaimodel.py:462-463): same RNG consumption
             torch.lt(self.u, self.p, out=self.mask)
         self.t.copy_(self.ts[i])
         if self.upd.NOISE:
             self.upd.draw(noise)
         self.coef.copy_(self.tab[i])
-        self.graph.replay()
+        if guided and self.scheduled:
+            self.w.copy_(self.wtab[i:i + 1])
+        (self.graph if guided else self.graph1).replay()
+        self.replays["guided" if guided else "cond"] += 1
 
     def final(self):
         return self.img.clone()                         # the static buffer belongs to the cached graph
@@ -401,7 +527,9 @@ class _GraphedStep:
 class _EagerStep:
     """The same step launched kernel by kernel, with the captured step's surface (``step``, ``img``, ``x0``, ``final``).  It
     covers what the capture leaves out: a generic ``denoise_sample_fn`` (guided NCHW eps), the ``cond_scale`` 0 / 1
-    shortcuts, ``p0``, ``hip_graph=False``, a given eps (PLMS), noise dropout and dynamic thresholding.  RNG order per step
+    shortcuts, ``p0``, ``hip_graph=False``, a given eps (PLMS), noise dropout and dynamic thresholding.  A scheduled
+    trajectory (``cfg_interval`` / ``cfg_rescale``) tells ``_StepRunner.eps`` per evaluation whether it is guided (host table)
+    and hands it the weight as a device float; ``replays`` counts the two kinds.  RNG order per step
     as in the reference: the cond-drop ``uniform_`` inside the UNet call, then ``z`` (drawn at eta = 0 too).  The
     trajectory's table is uploaded once and a step hands the kernel the address of its row; the image ping-pongs between
     two buffers (PLMS goes ``back`` to the pre-step one)."""
@@ -415,14 +543,28 @@ class _EagerStep:
         self.ts, self.tab = _t_rows(times, B, img.device), tab.to(img.device).contiguous()
         assert tuple(self.tab.shape[1:]) == upd.COEF[:1] and self.tab.dtype == upd.COEF[1]
         self.row0, self.row_bytes = self.tab.data_ptr(), self.tab.shape[1] * self.tab.element_size()
+        # scheduled guidance: per evaluation, whether it is guided (host) and its weight (device)
+        self.flags = self.wtab = None
+        if runner.scheduled:
+            self.flags, ws = runner.schedule(times)
+            self.wtab = torch.tensor(ws, dtype=torch.float32, device=img.device)
+        self.replays = dict(guided=0, cond=0)
 
     x0 = property(lambda self: self.upd.x0)
+
+    def eps(self, i, x=None):
+        """the UNet evaluation of schedule row i at ``x`` (default: the current image), as ``_StepRunner.eps`` returns it"""
+        x = self.img if x is None else x
+        if self.flags is None:
+            return self.runner.eps(x, self.ts[i])
+        self.replays["guided" if self.flags[i] else "cond"] += 1
+        return self.runner.eps(x, self.ts[i], self.flags[i], self.wtab[i:i + 1])
 
     def step(self, i, noise=None, want_x0=False, eps=None):
         """schedule row i from ``img``; ``eps``: a guided NCHW eps to use instead of evaluating the UNet at ``ts[i]``"""
         img, (B, Cc, hw) = self.img, self.dims
         # a guided NCHW eps is "NHWC with one channel" over B*C planes
-        e, mode, w, bb, cc = self.runner.eps(img, self.ts[i]) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
+        e, mode, w, bb, cc = self.eps(i) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
         opts = dict(z=self.upd.draw(noise, static=False), want_x0=want_x0) if self.upd.NOISE else {}
         self.upd.launch(_stream(), img, e, mode, w, bb, cc, hw, self.row0 + i * self.row_bytes, self.nxt, **opts)
         self.img, self.nxt = self.nxt, img
@@ -648,8 +790,8 @@ class DDIMSampler(object):
         B, Cc, hw = stepper.dims
         draws = iter(range(total + 1))
 
-        def guided(x, ts):
-            eps, mode, w, bb, cc = runner.eps(x, ts)
+        def guided(x, index):
+            eps, mode, w, bb, cc = stepper.eps(index, x)
             if mode == 0 and cc == 1:               # one-channel planes: NCHW already (else [B, hw, C], whatever the mode)
                 return eps.reshape(shape).clone()
             out = torch.empty(shape, device=dev)
@@ -661,10 +803,10 @@ class DDIMSampler(object):
 
         old_eps = []
         for index in reversed(range(total)):
-            e_t = guided(stepper.img, stepper.ts[index])
+            e_t = guided(stepper.img, index)
             if len(old_eps) == 0:
                 stepper.step(index, noise(), eps=e_t)                   # x_prev of the plain step, only to evaluate eps at
-                e_t_prime = (e_t + guided(stepper.img, stepper.ts[max(index - 1, 0)])) / 2
+                e_t_prime = (e_t + guided(stepper.img, max(index - 1, 0))) / 2
                 stepper.back()
             elif len(old_eps) == 1:
                 e_t_prime = (3 * e_t - old_eps[-1]) / 2
@@ -729,8 +871,9 @@ class DDIMSampler(object):
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk, host=True)
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev)
         upd = _DDUpdate("ddim", sk, 1 if sk["clip_denoised"] else 0, sk["temperature"])
-        stepper = _sampler_step(_StepRunner(denoise_sample_fn, dkw, sk, dev), sk, img, upd, self.ddim_timesteps, self.step_table)
+        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, self.step_table)
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
         for index in (reversed(range(total)) if visit is None else map(int, visit)):

@@ -10,6 +10,13 @@ read as v, one sgd_v_to_eps launch per evaluation inside the captured step) and 
 profiles/vpred_vs_eps_c2.txt is
     python tools/bench_samplers.py --methods ddim dpmsolver --parameterization eps v --reps 5 --out profiles/vpred_vs_eps_c2.txt
 
+`--cfg-interval LO HI` (or `--cfg-middle FRAC`: per sampler, the interval that covers the middle FRAC of its evaluations)
+and / or `--cfg-rescale PHI` time the guidance schedule instead (sampling kwargs cfg_interval / cfg_rescale): per sampler the
+variants `guided` (no option: the fused step), `rescale` (guidance throughout + the guide launch), `interval` (cond-only
+evaluations at batch B outside it) and `cond` (an interval that hits nothing: every evaluation cond-only), ALTERNATING within
+each repetition in one process, so drift hits all of them alike; profiles/cfg_schedule_c2.txt is
+    python tools/bench_samplers.py --methods ddim dpmsolver --cfg-middle 0.4 --cfg-rescale 0.7 --reps 5 --out profiles/cfg_schedule_c2.txt
+
     python tools/bench_samplers.py [--prec f16x3] [--reps 3] [--native-reps 1] [--methods ...] [--parameterization ...]
 """
 import argparse
@@ -26,6 +33,84 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 
 
+def schedule_main(a, wl, model, data, diff, par):
+    """the guidance-schedule variants of every chosen sampler, alternating (module docstring)"""
+    from sgdm_amd.diffusion import cfg_schedule, make_ddim_timesteps
+    B, S = wl["batch"], wl["image"]
+    data_kw = dict(cond=data["cond"].cuda(), layout=None, cond_scale=2.0)
+    x_T = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(23)).cuda()
+    lines = [f"# tools/bench_samplers.py: C2 = {wl['desc'].split(',')[0]}, precision {a.prec}, parameterization {par}, captured steps",
+             f"# device {torch.cuda.get_device_name(0)}; whole p_sample_loop calls (uint8 tail included), synchronised wall clock;",
+             f"# per sampler the variants alternate within each of the {a.reps} repetitions (one untimed run of each first)",
+             f"{'sampler':10s} {'variant':9s} {'interval':>11s} {'guided':>7s} {'cond':>5s} {'ms/trajectory (best)':>21s} {'median':>9s} "
+             f"{'vs guided':>10s} {'ms/eval (best)':>15s}"]
+    notes = []
+    for method, steps in (("ddim", 50), ("dpmsolver", 20)):
+        if method not in a.methods:
+            continue
+        skw = dict(sampling_method=method, vis=None, num_timesteps=steps, ddim_eta=0.0, log_num_per_prog=10, clip_denoised=True,
+                   dtp=1, temperature=1.0, noise_dropout=0, random_sample_condition=False, return_inter_dict=True,
+                   disable_tqdm=True, hip_graph=True)
+        if method == "ddim":
+            times = [int(t) for t in make_ddim_timesteps("uniform", steps, 1000)]
+        else:
+            times = [int(t) for t in diff.sampler_list[method].plan(dict(skw, alphas_cumprod=diff.sampler.alphas_cumprod))[0]]
+        E = len(times)
+        if a.cfg_middle is not None:
+            u = sorted(times)
+            n_in = max(1, round(a.cfg_middle * E))
+            lo = (E - n_in) // 2
+            iv = (u[lo], u[lo + n_in - 1])
+        else:
+            iv = tuple(a.cfg_interval) if a.cfg_interval else None
+        variants = [("guided", {})]
+        if a.cfg_rescale:
+            variants.append(("rescale", dict(cfg_rescale=a.cfg_rescale)))
+        if iv is not None:
+            variants += [("interval", dict(cfg_interval=iv)), ("cond", dict(cfg_interval=(0, 0)))]
+            if a.cfg_rescale:
+                variants.append(("both", dict(cfg_interval=iv, cfg_rescale=a.cfg_rescale)))
+        secs = {name: [] for name, _ in variants}
+        with torch.no_grad():
+            for rep in range(a.reps + 1):               # (the first round is the untimed one: engines, captures)
+                for name, opt in variants:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    u8, _ = diff.p_sample_loop(method, (B, 3, S, S), dict(skw, **opt), denoise_sample_fn_kwargs=dict(data_kw),
+                                               condition_kwargs={}, x_T=x_T)
+                    torch.cuda.synchronize()
+                    if rep:
+                        secs[name].append(time.perf_counter() - t0)
+                    assert u8.dtype == torch.uint8
+        best = {k: min(v) * 1e3 for k, v in secs.items()}
+        med = {k: statistics.median(v) * 1e3 for k, v in secs.items()}
+        for name, opt in variants:
+            flags = cfg_schedule(times, 2.0, model._scale_mode(), opt.get("cfg_interval"))[0]
+            ng = sum(flags)
+            ivs = "-" if "cfg_interval" not in opt else "%d..%d" % opt["cfg_interval"]
+            lines.append(f"{method:10s} {name:9s} {ivs:>11s} {ng:7d} {E - ng:5d} {best[name]:21.2f} {med[name]:9.2f} "
+                         f"{best[name] / best['guided'] - 1:+10.2%} {best[name] / E:15.3f}")
+            print(lines[-1], flush=True)
+        g = best["guided"] / E
+        if "cond" in best:
+            c = best["cond"] / E
+            ng = sum(cfg_schedule(times, 2.0, model._scale_mode(), iv)[0])
+            model_ms = ng * g + (E - ng) * c
+            notes.append(f"# {method}: a cond-only evaluation (UNet at batch {B}) {c:.3f} ms against a guided one (batch {2 * B}) "
+                         f"{g:.3f} ms: {c / g:.1%}; interval run {best['interval']:.1f} ms against {model_ms:.1f} ms = "
+                         f"{ng} x guided + {E - ng} x cond-only")
+        if "rescale" in best:
+            notes.append(f"# {method}: the guide launch (rescale {a.cfg_rescale}) costs {(best['rescale'] - best['guided']) / E:+.3f} ms per "
+                         f"evaluation (best against best; medians {(med['rescale'] - med['guided']) / E:+.3f})")
+        notes.append(f"# {method}: best-to-median spread of ms/trajectory: "
+                     + ", ".join(f"{k} {med[k] / best[k] - 1:.2%}" for k in best))
+    text = "\n".join(lines + notes) + "\n"
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3", "bf16x3", "f16", "bf16"])
@@ -35,6 +120,9 @@ def main():
                     choices=["ddim", "pndm", "dpmsolver", "native"])
     ap.add_argument("--parameterization", nargs="+", default=["eps"], choices=["eps", "v"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dpmsolver_vs_ddim_c2.txt"))
+    ap.add_argument("--cfg-interval", nargs=2, type=int, metavar=("LO", "HI"), default=None)
+    ap.add_argument("--cfg-middle", type=float, default=None, metavar="FRAC")
+    ap.add_argument("--cfg-rescale", type=float, default=0.0, metavar="PHI")
     a = ap.parse_args()
     from sgdm_amd.diffusion import LatentDiffusion
     wl = bench.WORKLOADS["c2"]
@@ -43,6 +131,8 @@ def main():
     for par in a.parameterization:
         diffs[par] = LatentDiffusion(device="cuda", **dict(bench.MODEL_PARAMS, parameterization=par))
         diffs[par].set_denoise_fn(model.forward, model.forward_with_cond_scale)
+    if a.cfg_interval or a.cfg_middle is not None or a.cfg_rescale:
+        return schedule_main(a, wl, model, data, diffs[a.parameterization[0]], a.parameterization[0])
     B, S = wl["batch"], wl["image"]
     dkw = dict(cond=data["cond"].cuda(), layout=None, cond_scale=2.0)
     x_T = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(23)).cuda()
