@@ -422,6 +422,33 @@ int sgd_dpmpp_step(const float* x, const float* eps_nhwc, int32_t cfg_mode, floa
  * (ABI unchanged at 24). */
 int sgd_v_to_eps(const float* x, const float* v_out, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                  int32_t cfg_mode, float w, int32_t b, int32_t c, int32_t hw, float* eps_out, void* stream);
+/* Data-form update for parameterization 'v' (sampling kwarg v_form='data', sgdm_amd/diffusion.py; no counterpart in the
+ * reference): ONE launch per UNet evaluation that reads the network output as v and performs the 'native', 'ddim' or
+ * 'dpmsolver' update without ever dividing by sa = sqrt(ac) -- the form a zero-terminal-SNR schedule (Lin et al. 2023,
+ * section 3.1: ac[T-1] = 0) needs, and one launch fewer than sgd_v_to_eps + update kernel on any schedule.  Per element, with
+ * a = sqrt_ac[t[n]], s = sqrt_1mac[t[n]], each product rounded before it is added, in this order:
+ *   vg  = guided(v_out)                      (the three cfg_mode forms above)
+ *   x0  = a * x - s * vg                     (finite at a == 0);   eps = a * vg + s * x     (the bits of sgd_v_to_eps)
+ *   clip != 0: x0 = min(max(x0, -1), 1)
+ *   acc = kx * x + k0 * x0
+ *   ke != 0: acc = acc + ke * eps;   kh != 0: acc = acc + kh * x0_hist;   kz != 0: acc = acc + kz * z
+ *   x0_hist = x0;   x_out = acc
+ * x0_hist [b*c*hw] is the step's x0 output and the multistep history; it is NOT read when kh == 0 (it may be uninitialised)
+ * and z is NOT read when kz == 0 (z may be NULL when no row has noise).  Rows, formed by the caller in double and rounded once:
+ *   native    : kx = posterior_mean_coef2, k0 = posterior_mean_coef1, kz = exp(0.5 posterior_log_variance) * temperature (0 at t = 0)
+ *   ddim      : k0 = sqrt(a_prev), ke = sqrt(1 - a_prev - sigma^2), kz = sigma * temperature
+ *   dpmsolver : kx = A, k0 = B * cc, kh = B * cp                  (A, B, cc, cp of sgd_dpmpp_row)
+ * v_out is laid out like eps_nhwc (cfg_mode 0: [b, hw, c]; a guided NCHW output is b*c one-channel planes, c = 1 and one t
+ * per plane); x, z, x0_hist, x_out are NCHW.  t is DEVICE int64 [b], the tables are the fp32 schedule buffers of
+ * sgd_q_sample, the row is read from DEVICE memory: no by-value argument changes between steps, so one captured step replays
+ * for a whole trajectory.  x_out == x allowed; x0_hist must not alias x, z or x_out.  Additive entry (ABI unchanged at 25). */
+typedef struct sgd_vstep_row {
+    float kx, k0, ke, kz, kh, pad0, pad1, pad2;
+} sgd_vstep_row;
+int sgd_v_step(const float* x, const float* v_out, const float* z /* may be NULL when kz == 0 in every row */,
+               int32_t cfg_mode, float w, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+               const sgd_vstep_row* row_dev, float* x0_hist, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
+               void* stream);
 /* Guidance pass (sampling kwargs cfg_interval / cfg_rescale, sgdm_amd/diffusion.py; no counterpart in the reference): the
  * guided network output, formed BEFORE the update instead of inside it, with the weight read from DEVICE memory -- no
  * by-value argument changes between steps, so one captured step serves a whole trajectory and any per-step weight schedule --

@@ -37,6 +37,8 @@ FILE_FLAGS["dpm.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["vpred.hip"] = ["-ffp-contract=off"]
 # guide.hip: the same -- the guided forms of the guidance pass (sgd_cfg_guide), product by product
 FILE_FLAGS["guide.hip"] = ["-ffp-contract=off"]
+# vstep.hip: the same -- the data-form update of parameterization 'v' (sgd_v_step), product by product
+FILE_FLAGS["vstep.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

@@ -155,6 +155,7 @@ SIGNATURES = {
     "sgd_q_sample_v": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp]),
     "sgd_v_to_eps": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, vp, vp]),
     "sgd_cfg_guide": (i32, [vp, i32, vp, f32, i32, i32, i32, vp, vp]),
+    "sgd_v_step": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, dvp, vp, i32, i32, i32, i32, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

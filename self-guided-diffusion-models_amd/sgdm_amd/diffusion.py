@@ -13,6 +13,12 @@ Also without a counterpart: the guidance schedule, sampling kwargs ``cfg_interva
 guidance only on evaluations whose time lies in the interval, the others ONE evaluation at B) and ``cfg_rescale`` = phi (Lin et
 al. 2023, section 3.4), honoured by all five samplers: ``cfg_options`` / ``cfg_schedule`` (host), ``_StepRunner.guide``
 (include/sgdm_hip.h: sgd_cfg_guide) between the UNet and everything that reads its output, with mode 0 from there on.
+Also without a counterpart, the rest of Lin et al. 2023: the hparam ``zero_terminal_snr`` (``zero_terminal_snr_betas``: the
+schedule rescaled so that alphas_cumprod[T-1] == 0; 'v' or 'x0' only), the sampling kwarg ``timestep_spacing`` = 'trailing'
+(``make_ddim_timesteps``: 'ddim', 'plms' and 'dpmsolver' start at the last timestep) and the sampling kwarg ``v_form`` = 'data'
+(``v_form_option``, ``_VUpdate``, include/sgdm_hip.h: sgd_v_step): 'native', 'ddim' and 'dpmsolver' read the network output as v
+and update from x0 = sa x - s1 v, eps = sa v + s1 x in ONE launch that never divides by sa -- what a schedule with sa = 0 needs,
+and what ``p_sample_loop`` chooses for a model with the hparam.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -61,8 +67,29 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     return betas.numpy()
 
 
-def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=False):
-    """util.py:46-60"""
+def zero_terminal_snr_betas(betas):
+    """Lin et al. 2023, Algorithm 1, in float64: sqrt(alphas_cumprod) shifted so that its last entry is 0 and scaled so that
+    its first entry stays, betas recovered from the result.  betas[-1] == 1 and cumprod(1 - betas)[-1] == 0 exactly"""
+    betas = np.asarray(betas, dtype=np.float64)
+    s = np.sqrt(np.cumprod(1.0 - betas))
+    s0, sT = s[0], s[-1]
+    s = (s - sT) * s0 / (s0 - sT)
+    ab = s ** 2
+    return 1.0 - np.concatenate([ab[:1], ab[1:] / ab[:-1]])
+
+
+def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=False, timestep_spacing="leading"):
+    """util.py:46-60 (``timestep_spacing`` 'leading'); 'trailing' (not in the reference; Lin et al. 2023, section 3.3): S
+    table indices that END at the last timestep, round(arange(T, 0, -T/S))[::-1] - 1, used as they are (no + 1)"""
+    if timestep_spacing == "trailing":
+        if ddim_discr_method != "uniform":
+            raise ValueError(f"timestep_spacing='trailing' goes with the 'uniform' discretization, not '{ddim_discr_method}'")
+        T, S = int(num_ddpm_timesteps), int(num_ddim_timesteps)
+        if not 1 <= S <= T:
+            raise ValueError(f"timestep_spacing='trailing': num_timesteps={S} (1 .. {T})")
+        return np.round(np.arange(T, 0, -T / S))[::-1].astype(np.int64) - 1
+    if timestep_spacing != "leading":
+        raise ValueError(f"timestep_spacing={timestep_spacing!r} ('leading' or 'trailing')")
     if ddim_discr_method == "uniform":
         c = num_ddpm_timesteps // num_ddim_timesteps
         ddim_timesteps = np.asarray(list(range(0, num_ddpm_timesteps, c)))
@@ -132,6 +159,37 @@ def cfg_options(sk, fused=True):
     return float(phi), iv
 
 
+V_FORM_SAMPLERS = ("native", "ddim", "dpmsolver")
+
+
+def v_form_option(sk, method, ac_visited=None, par=None):
+    """'eps' | 'data': the sampling kwarg ``v_form`` of a 'v' trajectory.  'eps' (default): the network output is changed to
+    eps (sgd_v_to_eps) and the sampler's own kernel forms x0 = (x - s1 eps) / sa.  'data': ONE launch (sgd_v_step) forms
+    x0 = sa x - s1 v and eps = sa v + s1 x and performs the update from them, finite at sa = 0.  ValueError, before anything
+    is loaded or launched, for 'data' with a parameterization other than 'v' (``par``: the one in force when the kwargs leave
+    it to the schedule), with dynamic thresholding, or on 'plms' / 'pndm' (multistep methods on eps; 'pndm' keeps a schedule of
+    its own); and for an eps-form trajectory that visits an ``alphas_cumprod`` of 0 (``ac_visited``: the table entries of the
+    visited times), where x0 = 0 / 0.  Pure host code: no device, no library."""
+    sk = sk or {}
+    form = sk.get("v_form", "eps")
+    if form not in ("eps", "data"):
+        raise ValueError(f"v_form={form!r} ('eps' or 'data')")
+    if form == "data":
+        par = sk.get("parameterization", "eps") if par is None else par
+        if par != "v":
+            raise ValueError(f"v_form='data' reads the network output as v: parameterization '{par}' has no data form")
+        if sk.get("dtp", 1) < 1.0:
+            raise ValueError("v_form='data': dynamic thresholding (dtp < 1) is not implemented on the data form")
+        if method not in V_FORM_SAMPLERS:
+            raise ValueError(f"v_form='data' is implemented for {', '.join(V_FORM_SAMPLERS)}; '{method}' is a multistep method "
+                             "on eps")
+    elif ac_visited is not None and bool((np.asarray(ac_visited, dtype=np.float64) == 0.0).any()):
+        raise ValueError(f"'{method}' on the eps form visits a time whose alphas_cumprod is 0 (a zero-terminal-SNR schedule): "
+                         "x0 = (x - s1 eps) / sa is 0 / 0 there.  Use parameterization='v' with v_form='data' (native, ddim, "
+                         "dpmsolver), or a timestep spacing that does not visit it")
+    return form
+
+
 def cfg_schedule(times, cond_scale, scale_mode, interval=None):
     """per UNet EVALUATION of a trajectory (``times``: its time argument, one entry per evaluation -- PNDM's list repeats
     times): (guided, weight).  An evaluation is guided when ``t_lo <= t <= t_hi`` (``interval`` None: always) and then has
@@ -148,7 +206,9 @@ class _StepRunner:
     """one sampling step = UNet(2B) + one fused update kernel (+ the v -> eps pass between them when ``sk`` says
     parameterization='v').  With ``cfg_rescale`` / ``cfg_interval`` in ``sk`` (``scheduled``) a guided evaluation puts the
     guide pass (sgd_cfg_guide) behind the UNet and everything after it reads the guided buffer with mode 0; an evaluation
-    outside the interval is ONE UNet evaluation at B, nothing dropped"""
+    outside the interval is ONE UNet evaluation at B, nothing dropped.  On the data form of 'v' (``form`` 'data') there is no
+    v -> eps pass: ``eps`` returns the network output (or the guided buffer) as it is and the update (_VUpdate, sgd_v_step)
+    takes the UNet's time and the two schedule tables, one launch fewer per evaluation"""
 
     def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
         self.fn = denoise_sample_fn
@@ -156,6 +216,8 @@ class _StepRunner:
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
         self.rescale, self.interval = cfg_options(sk, self.fused_cfg())        # refused before anything is loaded or launched
         self.scheduled = self.rescale > 0 or self.interval is not None
+        # 'data' (sampling kwarg v_form, checked by the sampler: v_form_option): no v -> eps pass, the update reads v itself
+        self.form = "data" if (sk or {}).get("parameterization", "eps") == "v" and (sk or {}).get("v_form") == "data" else "eps"
         self.lib = L.load()
         self._drop = {}
         self.v = _v_tables(sk, dev)
@@ -215,11 +277,13 @@ class _StepRunner:
                 if self.scheduled:
                     g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
                     out, mode, w = self.guide(out, mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), 0, 0.0
-            if self.v is None:
+            if self.v is None or self.form == "data":       # the data-form update reads v itself, with this mode and weight
                 return out, mode, w, B, Cc
             e = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
             return self.v_to_eps(x, out, t, mode, w, B, Cc, e, _stream()), 0, 0.0, B, Cc
         e = self.fn(x, t, **self.kwargs).contiguous()       # generic path: guided output, NCHW
+        if self.form == "data":
+            return e.float(), 0, 0.0, B * Cc, 1
         if self.v is not None:
             # B*C one-channel planes, one time per plane
             e = self.v_to_eps(x, e.float(), t.repeat_interleave(Cc), 0, 0.0, B * Cc, 1, torch.empty_like(x), _stream())
@@ -351,6 +415,35 @@ class _DPMUpdate(_Update):
                                         _ptr(x_out), st), "sgd_dpmpp_step")
 
 
+class _VUpdate(_Update):
+    """``sgd_v_step``: the data form of parameterization 'v' for 'native', 'ddim' and 'dpmsolver' (kinds 'v_native', 'v_ddim',
+    'v_dpmsolver').  A row is one ``sgd_vstep_row`` (include/sgdm_hip.h); it carries everything the samplers' own kernels take
+    by value (the DDIM temperature is folded into ``kz``), so the kind only says whose rows these are.  ``x0`` is the clipped
+    data prediction the snapshots log and the history a 'dpmsolver' row with ``kh != 0`` reads; a trajectory's first row has
+    ``kh == 0``.  ``launch`` also takes the UNet's time ``t`` [B] and the two schedule tables.  ``noise``: the sampler draws a
+    ``z`` per step ('native', 'ddim': in the reference's order, at eta = 0 too) and honours noise dropout, eager only."""
+
+    COEF = (8, torch.float32)
+
+    def __init__(self, kind, sk, clip, noise):
+        super().__init__(kind, sk, clip)
+        self.NOISE = bool(noise)
+        self.noise_dropout = sk.get("noise_dropout", 0) if noise else 0
+
+    def alloc(self, img):
+        self.x0 = torch.empty_like(img)
+        self.z = torch.empty_like(img) if self.NOISE else None
+
+    draw = _DDUpdate.draw
+
+    def launch(self, st, x, v, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+        if t.numel() != b:                                  # b = B * C one-channel planes (generic path): one time per plane
+            t = t.repeat_interleave(b // t.numel())
+        sa, s1 = tables
+        L.check(self.lib.sgd_v_step(_ptr(x), _ptr(v), _ptr(self.z if z is None else z), mode, w, _ptr(t), _ptr(sa), _ptr(s1),
+                                    row_dev, _ptr(self.x0), self.clip, b, c, hw, _ptr(x_out), st), "sgd_v_step")
+
+
 class _GraphedStep:
     """One CFG sampling step -- UNet at 2B (~135 launches) + the fused update -- captured into a hipGraph
     (``torch.cuda.CUDAGraph`` capture of the stream the C-ABI launchers are given), cached on the model per
@@ -382,7 +475,8 @@ class _GraphedStep:
         prec = L.PREC_BY_NAME[m.hip_precision]
         eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec)
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
-        par = "eps" if runner.v is None else ("v", runner.v[0].numel())
+        # (the data form of 'v' captures another update launch and no conversion: a third kind of entry)
+        par = "eps" if runner.v is None else ("v", runner.v[0].numel()) + (("data",) if runner.form == "data" else ())
         # a scheduled step reads its weight from the device: a sweep over weights or intervals reuses one capture (a pair
         # of graphs, when an interval is requested, is one entry)
         w = None if runner.scheduled else float(kw["cond_scale"])
@@ -427,7 +521,8 @@ class _GraphedStep:
         w, mode = float(kw["cond_scale"]), m._scale_mode()
         # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
         self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
-        self.veps = None if runner.v is None else torch.empty((B, hw, Cc), device=dev)
+        data = runner.form == "data"                    # the update reads v itself, at the static t, from the static tables
+        self.veps = None if runner.v is None or data else torch.empty((B, hw, Cc), device=dev)
         # scheduled guidance: this step's weight and the guided output
         self.scheduled = runner.scheduled
         self.w = torch.zeros(1, device=dev) if self.scheduled else None
@@ -436,6 +531,8 @@ class _GraphedStep:
         self.replays = dict(guided=0, cond=0)
 
         def tail(st, eps, mode, w):
+            if data:
+                return upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img, t=self.t, tables=self.v)
             if self.v is not None:                      # v -> guided eps at this step's time; the update reads it with mode 0
                 eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
             # reads ``eps`` (the UNet's output in the engine, the guided buffer or the converted eps), updates img in place
@@ -566,6 +663,8 @@ class _EagerStep:
         # a guided NCHW eps is "NHWC with one channel" over B*C planes
         e, mode, w, bb, cc = self.eps(i) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
         opts = dict(z=self.upd.draw(noise, static=False), want_x0=want_x0) if self.upd.NOISE else {}
+        if self.runner.form == "data":                  # the update reads v: it also takes the UNet's time and the two tables
+            opts.update(t=self.ts[i], tables=self.runner.v)
         self.upd.launch(_stream(), img, e, mode, w, bb, cc, hw, self.row0 + i * self.row_bytes, self.nxt, **opts)
         self.img, self.nxt = self.nxt, img
 
@@ -582,6 +681,7 @@ def _sampler_step(runner, sk, img, upd, times, tab, capture=True):
     drop-in UNet and nothing asked of the update that only the eager step runs (noise dropout, dynamic thresholding -- an
     update that does not honour them never sees them); ``hip_graph=False`` in the sampling kwargs (or SGDM_HIP_GRAPH=0) and
     ``capture=False`` (PLMS: the eps is the caller's) turn the capture off"""
+    assert isinstance(upd, _VUpdate) == (runner.form == "data"), (upd.kind, runner.form)
     on = capture and sk.get("hip_graph", True) and os.environ.get("SGDM_HIP_GRAPH", "1") != "0"
     if on and runner.fused_cfg() and upd.noise_dropout == 0 and upd.dtp >= 1.0:
         return _GraphedStep.get(runner, img, upd, times, tab)
@@ -616,6 +716,11 @@ class Schedule_DDPM(nn.Module):
         super().__init__()
         self.hparams = _Obj(kwargs)
         h = self.hparams
+        # optional hparam (not in the reference; Lin et al. 2023, section 3.1): the schedule rescaled to zero terminal SNR
+        self.zero_terminal_snr = bool(getattr(h, "zero_terminal_snr", False))
+        if self.zero_terminal_snr and h.parameterization == "eps":
+            raise ValueError("zero_terminal_snr with parameterization='eps': at SNR 0 the input is the noise, so the target "
+                             "carries no information; use 'v' (or 'x0')")
         self.register_schedule(given_betas=h.given_betas, beta_schedule=h.beta_schedule, timesteps=h.num_timesteps,
                                linear_start=h.linear_start, linear_end=h.linear_end, cosine_s=h.cosine_s)
 
@@ -628,6 +733,8 @@ class Schedule_DDPM(nn.Module):
             return                       # the reference rebuilds identical buffers on every sample() call
         betas = given_betas if given_betas is not None else make_beta_schedule(
             beta_schedule, h.num_timesteps, linear_start=linear_start, linear_end=linear_end, cosine_s=cosine_s)
+        if self.zero_terminal_snr:
+            betas = zero_terminal_snr_betas(betas)          # betas[-1] == 1, alphas_cumprod[-1] == 0
         alphas = 1. - betas
         alphas_cumprod = np.cumprod(alphas, axis=0)
         alphas_cumprod_prev = np.append(1., alphas_cumprod[:-1])
@@ -644,8 +751,9 @@ class Schedule_DDPM(nn.Module):
         reg("sqrt_alphas_cumprod", to_torch(np.sqrt(alphas_cumprod)))
         reg("sqrt_one_minus_alphas_cumprod", to_torch(np.sqrt(1. - alphas_cumprod)))
         reg("log_one_minus_alphas_cumprod", to_torch(np.log(1. - alphas_cumprod)))
-        reg("sqrt_recip_alphas_cumprod", to_torch(np.sqrt(1. / alphas_cumprod)))
-        reg("sqrt_recipm1_alphas_cumprod", to_torch(np.sqrt(1. / alphas_cumprod - 1)))
+        with np.errstate(divide="ignore"):              # zero terminal SNR: both are inf at T-1 (and so is lvlb_weights for
+            reg("sqrt_recip_alphas_cumprod", to_torch(np.sqrt(1. / alphas_cumprod)))          # 'v'); the data form of 'v' and
+            reg("sqrt_recipm1_alphas_cumprod", to_torch(np.sqrt(1. / alphas_cumprod - 1)))    # the 'x0' rows never read them
         vp = h.v_posterior
         posterior_variance = (1 - vp) * betas * (1. - alphas_cumprod_prev) / (1. - alphas_cumprod) + vp * betas
         reg("posterior_variance", to_torch(posterior_variance))
@@ -708,6 +816,16 @@ class Schedule_DDPM(nn.Module):
         tab[0, 4] = 0.0
         return tab.float()
 
+    def vstep_table(self, temperature):
+        """[T, 8] fp32 rows of sgd_v_step (sgd_vstep_row) for one trajectory on the data form of 'v': kx = posterior_mean_coef2,
+        k0 = posterior_mean_coef1, kz = the noise scale of ``step_table``; all finite on a zero-terminal-SNR schedule (T-1:
+        kx = 0, k0 = sqrt(ac_prev), kz = sqrt(1 - ac_prev))"""
+        tab = torch.zeros(self._step_tab.shape[0], 8, dtype=torch.float64)
+        tab[:, 0], tab[:, 1] = self._step_tab[:, 3].double(), self._step_tab[:, 2].double()
+        tab[:, 3] = self._step_tab[:, 4].double() * torch.tensor([float(v) for v in temperature], dtype=torch.float64)
+        tab[0, 3] = 0.0
+        return tab.float()
+
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, denoise_sample_fn=None, denoise_sample_fn_kwargs=None, **kwargs):
         """ancestral DDPM loop (ddpm_sampler.py:194-238); ``x_T`` / ``noise_fn(i)`` may be injected for tests"""
@@ -723,15 +841,23 @@ class Schedule_DDPM(nn.Module):
             # a direct call: this object is the training schedule, so its own hparam and buffers stand in for the kwargs
             sk = dict(sk, parameterization="v", sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
                       sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
+        order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
+        # the 'x0' rows (0, -1) never read the infinite entries of a zero-terminal-SNR table: nothing to refuse there
+        visited = None if h.parameterization == "x0" else self.alphas_cumprod.detach().cpu().numpy()[
+            list(range(timesteps)) if order is None else [int(i) for i in order]]
+        form = v_form_option(sk, "native", visited)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         if type(temperature) == float or isinstance(temperature, int):
             temperature = [float(temperature)] * timesteps
         snaps = _Snapshots(timesteps, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        stepper = _sampler_step(runner, sk, img, _DDUpdate("ddpm", sk, 1 if sk["clip_denoised"] else 0), range(timesteps),
-                                self.step_table(temperature))
-        order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
+        clip = 1 if sk["clip_denoised"] else 0
+        if form == "data":
+            upd, tab = _VUpdate("v_native", sk, clip, noise=True), self.vstep_table(temperature)
+        else:
+            upd, tab = _DDUpdate("ddpm", sk, clip), self.step_table(temperature)
+        stepper = _sampler_step(runner, sk, img, upd, range(timesteps), tab)
         for i in (reversed(range(0, timesteps)) if order is None else order):
             want = i in snaps.rows
             stepper.step(i, None if noise_fn is None else noise_fn(i).to(dev), want)
@@ -753,19 +879,40 @@ class DDIMSampler(object):
         if eta != 0 and self.sampler_type == "plms":
             eta = 0                                               # ddim_plms_sampler.py:41-45 (warns and resets)
         ac = sampling_kwargs["alphas_cumprod"]
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, S, self.ddpm_num_timesteps)
+        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, S, self.ddpm_num_timesteps,
+                                                  timestep_spacing=sampling_kwargs.get("timestep_spacing", "leading"))
         assert ac.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
         sig, a, ap = make_ddim_sampling_parameters(ac.detach().float().cpu(), self.ddim_timesteps, eta)
-        self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev = sig, a, ap
+        self.ddim_sigmas, self.ddim_alphas, self.ddim_alphas_prev, self.ddim_eta = sig, a, ap, float(eta)
         self.ddim_sqrt_one_minus_alphas = np.sqrt(1.0 - a)
         # [S, 5] fp32 rows of sgd_ddim_step (the fifth column, the DDPM rows' noise scale, stays 0): the table entries cast
         # to fp32 as torch.full_like(x, table[index]) does (ddim_plms_sampler.py:360-366)
         tab = np.stack([self.ddim_sqrt_one_minus_alphas, a, ap, sig, np.zeros_like(sig)], 1)
         self.step_table = torch.tensor(tab, dtype=torch.float64).float()
 
+    def vstep_table(self, temperature):
+        """[S, 8] fp32 rows of sgd_v_step (sgd_vstep_row) on the data form of 'v': k0 = sqrt(a_prev),
+        ke = sqrt(1 - a_prev - sigma^2), kz = sigma * temperature, float64 math from the fp32 a_t and a_prev of ``step_table``
+        and rounded once.  sigma is formed again in float64, not read from the table: ke's radicand,
+        a_t (1 - a_prev)^2 / (a_prev (1 - a_t)) at eta = 1, cancels as a_t -> 0 and is exactly 0 at a_t = 0, where a sigma
+        already rounded to fp32 leaves a ke of 2e-4 instead (the radicand is floored at 0 against the last float64 bit).  No
+        entry divides by a_t."""
+        st = self.step_table.double()
+        a, ap = st[:, 1], st[:, 2]
+        sig = self.ddim_eta * ((1.0 - ap) / (1.0 - a) * (1.0 - a / ap)).sqrt()
+        tab = torch.zeros(st.shape[0], 8, dtype=torch.float64)
+        tab[:, 1] = ap.sqrt()
+        tab[:, 2] = (1.0 - ap - sig * sig).clamp_min(0.0).sqrt()
+        tab[:, 3] = sig * float(temperature)
+        return tab.float()
+
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, **kwargs):
         self.make_schedule(sampling_kwargs=sampling_kwargs)
+        # step_indices (teacher-forced tests) visits only those table rows
+        rows = kwargs.get("step_indices") if self.sampler_type == "ddim" else None
+        times = self.ddim_timesteps if rows is None else self.ddim_timesteps[[int(i) for i in rows]]
+        v_form_option(sampling_kwargs, self.sampler_type, sampling_kwargs["alphas_cumprod"].detach().float().cpu().numpy()[times])
         if self.sampler_type == "ddim":
             return self.ddim_sampling(shape, sampling_kwargs=sampling_kwargs, **kwargs)
         if self.sampler_type == "plms":
@@ -872,8 +1019,12 @@ class DDIMSampler(object):
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk, host=True)
         runner = _StepRunner(denoise_sample_fn, dkw, sk, dev)
-        upd = _DDUpdate("ddim", sk, 1 if sk["clip_denoised"] else 0, sk["temperature"])
-        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, self.step_table)
+        clip = 1 if sk["clip_denoised"] else 0
+        if runner.form == "data":
+            upd, tab = _VUpdate("v_ddim", sk, clip, noise=True), self.vstep_table(sk["temperature"])
+        else:
+            upd, tab = _DDUpdate("ddim", sk, clip, sk["temperature"]), self.step_table
+        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, tab)
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
         for index in (reversed(range(total)) if visit is None else map(int, visit)):
@@ -956,6 +1107,7 @@ class PNDM_Sampler(object):
     def sample(self, shape, sampling_kwargs, log_num_per_prog=100, denoise_sample_fn=None, denoise_sample_fn_kwargs=None,
                **kwargs):
         sk = sampling_kwargs
+        v_form_option(sk, "pndm")                   # (its own schedule: no zero alphas_cumprod of the model's to visit)
         n = sk["num_timesteps"]
         times, tab = self.plan(n)
         if n > 250:
@@ -980,8 +1132,9 @@ class DPMSolverSampler(object):
     Sampling kwargs read: ``num_timesteps`` (S), ``alphas_cumprod``, ``clip_denoised``, ``log_num_per_prog``, and for direct
     callers ``dpm_spacing`` ('logsnr' | 'uniform' | 'quad', default 'logsnr'), ``dpm_order`` (1 | 2, default 2) and
     ``dpm_lower_order_final`` (default: fewer than 15 times).  ``ddim_eta``, ``temperature``, ``noise_dropout`` and ``vis`` are
-    ignored; ``dtp < 1`` is refused.  ``parameterization`` 'eps' (default; 'x0' is read as eps, like 'ddim' does) or 'v'.  Tests
-    may inject ``x_T=``."""
+    ignored; ``dtp < 1`` is refused.  ``parameterization`` 'eps' (default; 'x0' is read as eps, like 'ddim' does) or 'v'; 'v'
+    with ``v_form='data'`` runs ``sgd_v_step`` on the rows of ``plan(sk, 'data')`` instead.  ``timestep_spacing`` is honoured by
+    ``dpm_spacing='uniform'``.  Tests may inject ``x_T=``."""
 
     def __init__(self, ddpm_num_timesteps, device):
         self.ddpm_num_timesteps = ddpm_num_timesteps
@@ -996,14 +1149,19 @@ class DPMSolverSampler(object):
         if kind == "uniform":
             if S > T:
                 raise ValueError(f"dpmsolver: num_timesteps={S} > {T}")
-            ts = make_ddim_timesteps("uniform", S, T)
+            ts = make_ddim_timesteps("uniform", S, T, timestep_spacing=sampling_kwargs.get("timestep_spacing", "leading"))
         elif kind == "quad":
             ts = np.unique(make_ddim_timesteps("quad", S, T))
         elif kind == "logsnr":
             # uniform in log-SNR between the two ends of the table (DPM-Solver's recommendation for small images), each
             # target mapped to the nearest table entry
-            targets = np.linspace(lam[T - 1], lam[1], S)
-            ts = np.unique([1 + int(np.abs(lam[1:T] - v).argmin()) for v in targets])
+            if np.isneginf(lam[T - 1]):
+                # zero terminal SNR: the last entry itself, then S - 1 targets over the finite part of the table
+                targets = np.linspace(lam[T - 2], lam[1], S - 1)
+                ts = np.unique([T - 1] + [1 + int(np.abs(lam[1:T - 1] - v).argmin()) for v in targets])
+            else:
+                targets = np.linspace(lam[T - 1], lam[1], S)
+                ts = np.unique([1 + int(np.abs(lam[1:T] - v).argmin()) for v in targets])
         else:
             raise ValueError(f"dpmsolver: unknown dpm_spacing '{kind}' (logsnr, uniform, quad)")
         ts = np.asarray(ts, dtype=np.int64)
@@ -1013,17 +1171,20 @@ class DPMSolverSampler(object):
             raise ValueError(f"dpmsolver: num_timesteps={S} with dpm_spacing='{kind}' reaches table index {int(ts[-1])} >= {T}")
         return ts
 
-    def plan(self, sampling_kwargs):
-        """(ts, [len(ts), 8] fp32 table of sgd_dpmpp_row): row i is the step from table index ts[i] to ts[i-1] (to 0 for
-        i = 0); the trajectory visits the rows from the last to the first.  float64 math from the fp32 ``alphas_cumprod``,
-        rounded once."""
+    def plan(self, sampling_kwargs, form="eps"):
+        """(ts, [len(ts), 8] fp32 table): row i is the step from table index ts[i] to ts[i-1] (to 0 for i = 0); the trajectory
+        visits the rows from the last to the first.  float64 math from the fp32 ``alphas_cumprod``, rounded once.  ``form``
+        'eps': rows of sgd_dpmpp_row; 'data' (the data form of 'v'): rows of sgd_vstep_row, kx = A, k0 = B cc, kh = B cp --
+        nothing divides by sqrt(a_t).  On a zero-terminal-SNR table the first visited row has a_t = 0: A = sqrt(1 - a_prev),
+        B = sqrt(a_prev), h = +inf, and the infinite h makes the NEXT row's 1 / (2r) exactly 0, a first-order row."""
         sk = sampling_kwargs
         order = sk.get("dpm_order", 2)
         if order not in (1, 2):
             raise ValueError(f"dpmsolver: dpm_order={order!r} (1 or 2)")
         a = sk["alphas_cumprod"].detach().float().cpu().double().numpy()
         assert a.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
-        lam = 0.5 * np.log(a / (1.0 - a))
+        with np.errstate(divide="ignore"):
+            lam = 0.5 * np.log(a / (1.0 - a))               # -inf where a == 0
         ts = self.time_steps(sk, lam)
         n = len(ts)
         lof = sk.get("dpm_lower_order_final")
@@ -1031,14 +1192,20 @@ class DPMSolverSampler(object):
         at, ap = a[ts], np.concatenate([a[:1], a[ts[:-1]]])
         A = np.sqrt((1.0 - ap) / (1.0 - at))
         B = np.sqrt(ap) - A * np.sqrt(at)                   # alpha_prev (1 - exp(-h)) without logarithms
-        h = 0.5 * np.log(ap / (1.0 - ap)) - 0.5 * np.log(at / (1.0 - at))
+        with np.errstate(divide="ignore"):
+            h = 0.5 * np.log(ap / (1.0 - ap)) - 0.5 * np.log(at / (1.0 - at))
         cc, cp = np.ones(n), np.zeros(n)
         if order == 2:
             r = h[1:] / h[:-1]                              # row i follows row i + 1: r = h_prev / h
             cc[:-1], cp[:-1] = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
             if lof:
                 cc[0], cp[0] = 1.0, 0.0
-        tab = np.stack([np.sqrt(1.0 - at), 1.0 / np.sqrt(at), A, B, cc, cp, np.zeros(n), np.zeros(n)], 1)
+        zero = np.zeros(n)
+        if form == "data":
+            tab = np.stack([A, B * cc, zero, zero, B * cp, zero, zero, zero], 1)
+        else:
+            with np.errstate(divide="ignore"):
+                tab = np.stack([np.sqrt(1.0 - at), 1.0 / np.sqrt(at), A, B, cc, cp, zero, zero], 1)
         return ts, torch.tensor(tab, dtype=torch.float64).float()
 
     @torch.no_grad()
@@ -1046,14 +1213,18 @@ class DPMSolverSampler(object):
         sk = sampling_kwargs
         if sk.get("dtp", 1) < 1.0:
             raise ValueError("dpmsolver: dynamic thresholding (dtp < 1) is not implemented for this sampler")
-        ts, tab = self.plan(sk)
+        form = v_form_option(sk, "dpmsolver")
+        ts, tab = self.plan(sk, form)
+        v_form_option(sk, "dpmsolver", sk["alphas_cumprod"].detach().float().cpu().numpy()[ts])
         dev = torch.device(self.device)
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         total = len(ts)
         snaps = _Snapshots(total, sk)
-        stepper = _sampler_step(runner, sk, img, _DPMUpdate("dpmsolver", sk, 1 if sk["clip_denoised"] else 0), ts, tab)
+        clip = 1 if sk["clip_denoised"] else 0
+        upd = _VUpdate("v_dpmsolver", sk, clip, noise=False) if form == "data" else _DPMUpdate("dpmsolver", sk, clip)
+        stepper = _sampler_step(runner, sk, img, upd, ts, tab)
         for index in reversed(range(total)):
             stepper.step(index)
             if index in snaps.rows:
@@ -1073,8 +1244,8 @@ def to_uint8(x):
 
 class LatentDiffusion(nn.Module):
     """diffusion/ddpm.py:24-126 (parameterization eps|x0, loss l1|l2|huber; samplers native, ddim, plms and pndm --
-    the reference's 'tero' fails inside its own p_sample_loop; 'dpmsolver' and parameterization 'v'
-    are this project's own)"""
+    the reference's 'tero' fails inside its own p_sample_loop; 'dpmsolver', parameterization 'v' and the
+    hparam zero_terminal_snr are this project's own)"""
 
     def __init__(self, **kwargs):
         super().__init__()
@@ -1119,6 +1290,10 @@ class LatentDiffusion(nn.Module):
         if self.hparams.parameterization == "v":        # the tables the v -> eps pass gathers from: the training schedule's
             sk.update(dict(sqrt_alphas_cumprod=self.sampler.sqrt_alphas_cumprod,
                            sqrt_one_minus_alphas_cumprod=self.sampler.sqrt_one_minus_alphas_cumprod))
+            # a zero-terminal-SNR schedule is sampled on the data form wherever there is one (plms / pndm stay on eps: plms
+            # works as long as its spacing does not visit the last timestep, and is refused by the sampler when it does)
+            if self.sampler.zero_terminal_snr and sampling_method in V_FORM_SAMPLERS:
+                sk.setdefault("v_form", "data")
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(
             shape=shape, denoise_sample_fn=self.denoise_sample_fn, sampling_kwargs=sk, **kwargs)

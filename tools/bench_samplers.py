@@ -17,6 +17,12 @@ evaluations at batch B outside it) and `cond` (an interval that hits nothing: ev
 each repetition in one process, so drift hits all of them alike; profiles/cfg_schedule_c2.txt is
     python tools/bench_samplers.py --methods ddim dpmsolver --cfg-middle 0.4 --cfg-rescale 0.7 --reps 5 --out profiles/cfg_schedule_c2.txt
 
+`--v-form eps data` times the two forms of parameterization 'v' (sampling kwarg v_form: 'eps' = sgd_v_to_eps + the sampler's
+own update kernel, 'data' = ONE sgd_v_step launch) per chosen sampler (ddim-50, dpmsolver-20), ALTERNATING within each
+repetition in one process; `--zero-terminal-snr` builds the model's schedule with the hparam of that name (then only 'data'
+can visit the last timestep) and `--spacing trailing` sets the sampling kwarg timestep_spacing; profiles/ztsnr_c2.txt is
+    python tools/bench_samplers.py --methods ddim dpmsolver --parameterization v --v-form eps data --reps 5 --out profiles/ztsnr_c2.txt
+
     python tools/bench_samplers.py [--prec f16x3] [--reps 3] [--native-reps 1] [--methods ...] [--parameterization ...]
 """
 import argparse
@@ -111,6 +117,63 @@ def schedule_main(a, wl, model, data, diff, par):
     print(text)
 
 
+def forms_main(a, wl, model, data):
+    """the forms of 'v' of every chosen sampler, alternating (module docstring)"""
+    from sgdm_amd.diffusion import LatentDiffusion
+    hp = dict(bench.MODEL_PARAMS, parameterization="v", **(dict(zero_terminal_snr=True) if a.zero_terminal_snr else {}))
+    diff = LatentDiffusion(device="cuda", **hp)
+    diff.set_denoise_fn(model.forward, model.forward_with_cond_scale)
+    B, S = wl["batch"], wl["image"]
+    data_kw = dict(cond=data["cond"].cuda(), layout=None, cond_scale=2.0)
+    x_T = torch.randn(B, 3, S, S, generator=torch.Generator().manual_seed(23)).cuda()
+    lines = [f"# tools/bench_samplers.py: C2 = {wl['desc'].split(',')[0]}, precision {a.prec}, parameterization v, captured steps,",
+             f"# zero_terminal_snr {a.zero_terminal_snr}, timestep_spacing {a.spacing}",
+             f"# device {torch.cuda.get_device_name(0)}; whole p_sample_loop calls (uint8 tail included), synchronised wall clock;",
+             f"# per sampler the forms alternate within each of the {a.reps} repetitions (one untimed run of each first)",
+             f"{'sampler':10s} {'v_form':>6s} {'steps':>6s} {'UNet evals':>10s} {'ms/trajectory (best)':>21s} {'median':>9s} "
+             f"{'vs ' + a.v_form[0]:>8s} {'ms/eval (best)':>15s} {'launches/eval after the UNet':>29s}"]
+    notes = []
+    for method, steps in (("ddim", 50), ("dpmsolver", 20)):
+        if method not in a.methods:
+            continue
+        skw = dict(sampling_method=method, vis=None, num_timesteps=steps, ddim_eta=0.0, log_num_per_prog=10, clip_denoised=True,
+                   dtp=1, temperature=1.0, noise_dropout=0, random_sample_condition=False, return_inter_dict=True,
+                   disable_tqdm=True, hip_graph=True, timestep_spacing=a.spacing)
+        if method == "dpmsolver" and a.spacing == "trailing":
+            skw["dpm_spacing"] = "uniform"              # (the spacing kwarg is honoured by the uniform table; logsnr has its own)
+        E = steps if method == "ddim" else len(diff.sampler_list[method].plan(
+            dict(skw, alphas_cumprod=diff.sampler.alphas_cumprod), "data")[0])
+        secs = {form: [] for form in a.v_form}
+        with torch.no_grad():
+            for rep in range(a.reps + 1):               # (the first round is the untimed one: engines, captures)
+                for form in a.v_form:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    u8, _ = diff.p_sample_loop(method, (B, 3, S, S), dict(skw, v_form=form), denoise_sample_fn_kwargs=dict(data_kw),
+                                               condition_kwargs={}, x_T=x_T)
+                    torch.cuda.synchronize()
+                    if rep:
+                        secs[form].append(time.perf_counter() - t0)
+                    assert u8.dtype == torch.uint8
+        best = {k: min(v) * 1e3 for k, v in secs.items()}
+        med = {k: statistics.median(v) * 1e3 for k, v in secs.items()}
+        for form in a.v_form:
+            lines.append(f"{method:10s} {form:>6s} {steps:6d} {E:10d} {best[form]:21.2f} {med[form]:9.2f} "
+                         f"{best[form] / best[a.v_form[0]] - 1:+8.2%} {best[form] / E:15.3f} {2 if form == 'eps' else 1:29d}")
+            print(lines[-1], flush=True)
+        if len(a.v_form) > 1:
+            f0, f1 = a.v_form[0], a.v_form[1]
+            notes.append(f"# {method}: {f1} against {f0}: {(best[f1] - best[f0]) / E:+.4f} ms per evaluation best against best, "
+                         f"{(med[f1] - med[f0]) / E:+.4f} median against median")
+        notes.append(f"# {method}: best-to-median spread of ms/trajectory: "
+                     + ", ".join(f"{k} {med[k] / best[k] - 1:.2%}" for k in best))
+    text = "\n".join(lines + notes) + "\n"
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--prec", default="f16x3", choices=["f32", "f16x3", "bf16x3", "f16", "bf16"])
@@ -123,10 +186,17 @@ def main():
     ap.add_argument("--cfg-interval", nargs=2, type=int, metavar=("LO", "HI"), default=None)
     ap.add_argument("--cfg-middle", type=float, default=None, metavar="FRAC")
     ap.add_argument("--cfg-rescale", type=float, default=0.0, metavar="PHI")
+    ap.add_argument("--zero-terminal-snr", action="store_true")
+    ap.add_argument("--spacing", default="leading", choices=["leading", "trailing"])
+    ap.add_argument("--v-form", nargs="+", default=["eps"], choices=["eps", "data"])
     a = ap.parse_args()
     from sgdm_amd.diffusion import LatentDiffusion
     wl = bench.WORKLOADS["c2"]
     model, _, data = bench.build_model(wl, "cuda", a.prec)
+    if a.v_form != ["eps"] or a.zero_terminal_snr or a.spacing != "leading":
+        if a.parameterization != ["v"]:
+            ap.error("--v-form / --zero-terminal-snr / --spacing time parameterization 'v': pass --parameterization v")
+        return forms_main(a, wl, model, data)
     diffs = {}
     for par in a.parameterization:
         diffs[par] = LatentDiffusion(device="cuda", **dict(bench.MODEL_PARAMS, parameterization=par))
