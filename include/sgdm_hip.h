@@ -679,6 +679,26 @@ int sgd_conv3_narrow_out(const float* x, const float* pa, const float* pb, int32
 int sgd_mse_loss(const float* eps_nhwc, const float* noise_nchw, int32_t b, int32_t c, int32_t hw,
                  float* per_sample, float* geps_nhwc, void* stream);
 
+/* Weighted loss of the trained target and its gradient (csrc/loss.hip; additive entries, no counterpart in the reference, which
+ * weighs every timestep alike).  All tensors NCHW [b, chw]; t DEVICE int64 [b]; sqrt_ac / sqrt_1mac / wt DEVICE fp32 [T].
+ *   par  0 eps: target = noise | 1 x0: target = x0 | 2 v: target = sqrt_ac[t]*noise - sqrt_1mac[t]*x0 (the bits of
+ *        sgd_q_sample_v's v_out: each product rounded before the subtraction; never written to memory)
+ *   kind 0 l2: l = d*d | 1 l1: l = |d| | 2 huber: l = |d| < 1 ? 0.5*d*d : |d| - 0.5 (smooth_l1, beta 1),   d = out - target
+ * sgd_loss_fwd: per_raw[n] = mean_chw l (per-thread partial sums in double, folded in a fixed order: identical from run to
+ *   run), per_w[n] = wt[t[n]] * per_raw[n] (wt NULL: per_w = per_raw).  One workgroup per sample.
+ * sgd_loss_bwd: gout = d (sum_n gper[n] * per_w[n]) / d out * gscale, element-wise: per sample k = (gper[n] * wt[t[n]]) /
+ *   (float)chw, k = k * gscale; g = (2*k)*d (l2) | k*sign(d), sign(0) = 0 (l1) | k*min(max(d, -1), 1) (huber).  gper is read from
+ *   DEVICE memory and gscale is a constant of the caller, so no by-value argument depends on the step.
+ * Tensors the target does not read may be NULL (x0 for par 0, noise for par 1, the two tables unless par 2).  16-byte accesses
+ * when chw % 4 == 0 and every tensor is 16-byte aligned, one float per lane otherwise.  SGD_ERR_ARG, nothing launched: b <= 0,
+ * chw <= 0, par / kind out of range, a NULL pointer the call needs. */
+int sgd_loss_fwd(const float* out, const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
+                 const float* sqrt_1mac, const float* wt /* [T] or NULL = 1 */, int32_t par, int32_t kind, int32_t b, int64_t chw,
+                 float* per_raw /* [b] */, float* per_w /* [b] */, void* stream);
+int sgd_loss_bwd(const float* out, const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
+                 const float* sqrt_1mac, const float* wt, const float* gper /* DEVICE [b]: dL / d per_w */, float gscale,
+                 int32_t par, int32_t kind, int32_t b, int64_t chw, float* gout /* [b, chw] */, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * Optimizer step: AdamW (lightning_module_common.py:20-42: torch.optim.AdamW defaults, decoupled weight decay)
  * and the LitEma shadow update (dynamic/ema.py:25-44) of every parameter in ONE launch:

@@ -39,6 +39,8 @@ FILE_FLAGS["vpred.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["guide.hip"] = ["-ffp-contract=off"]
 # vstep.hip: the same -- the data-form update of parameterization 'v' (sgd_v_step), product by product
 FILE_FLAGS["vstep.hip"] = ["-ffp-contract=off"]
+# loss.hip: the same -- the weighted loss's target and gradient (sgd_loss_fwd / sgd_loss_bwd), product by product
+FILE_FLAGS["loss.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

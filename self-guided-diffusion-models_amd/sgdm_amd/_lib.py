@@ -156,6 +156,8 @@ SIGNATURES = {
     "sgd_v_to_eps": (i32, [vp, vp, vp, vp, vp, i32, f32, i32, i32, i32, vp, vp]),
     "sgd_cfg_guide": (i32, [vp, i32, vp, f32, i32, i32, i32, vp, vp]),
     "sgd_v_step": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, dvp, vp, i32, i32, i32, i32, vp, vp]),
+    "sgd_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
+    "sgd_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, dvp, f32, i32, i32, i32, i64, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

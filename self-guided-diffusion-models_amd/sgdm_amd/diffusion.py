@@ -19,6 +19,10 @@ schedule rescaled so that alphas_cumprod[T-1] == 0; 'v' or 'x0' only), the sampl
 (``v_form_option``, ``_VUpdate``, include/sgdm_hip.h: sgd_v_step): 'native', 'ddim' and 'dpmsolver' read the network output as v
 and update from x0 = sa x - s1 v, eps = sa v + s1 x in ONE launch that never divides by sa -- what a schedule with sa = 0 needs,
 and what ``p_sample_loop`` chooses for a model with the hparam.
+Also without a counterpart, on the training side: the hparam ``loss_weighting`` ('min_snr', Hang et al. 2023; 'trunc_snr',
+Salimans & Ho 2022; 'p2', Choi et al. 2022; 'table'): ``loss_weight_table`` builds the per-timestep weights on the loss of the
+trained target, ``Schedule_DDPM`` keeps them as the buffer ``loss_weights`` and ``train.p_losses_hip`` applies them inside the
+loss kernels (include/sgdm_hip.h: sgd_loss_fwd / sgd_loss_bwd).
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -76,6 +80,75 @@ def zero_terminal_snr_betas(betas):
     s = (s - sT) * s0 / (s0 - sT)
     ab = s ** 2
     return 1.0 - np.concatenate([ab[:1], ab[1:] / ab[:-1]])
+
+
+LOSS_WEIGHTINGS = ("min_snr", "trunc_snr", "p2", "table")
+
+
+def loss_weighting_option(h):
+    """the optional hparams ``loss_weighting`` (None / 'none': off; 'min_snr', 'trunc_snr', 'p2', 'table'),
+    ``loss_weighting_gamma`` (default 5 for 'min_snr', 1 for 'p2'), ``loss_weighting_k`` ('p2', default 1) and
+    ``loss_weighting_table`` (length T, 'table' only), validated: None when off, else (scheme, gamma, k, table as float64
+    numpy or None).  Raises ValueError -- at construction, nothing is loaded or launched before."""
+    scheme = getattr(h, "loss_weighting", None)
+    table = getattr(h, "loss_weighting_table", None)
+    if scheme in (None, "none"):
+        if table is not None:
+            raise ValueError("loss_weighting_table is given but loss_weighting is not 'table'")
+        return None
+    if scheme not in LOSS_WEIGHTINGS:
+        raise ValueError(f"loss_weighting={scheme!r}: one of {LOSS_WEIGHTINGS}, or None / 'none'")
+    gamma, k = getattr(h, "loss_weighting_gamma", None), getattr(h, "loss_weighting_k", None)
+    gamma = (1.0 if scheme == "p2" else 5.0) if gamma is None else float(gamma)
+    k = 1.0 if k is None else float(k)
+    if not (gamma > 0 and np.isfinite(gamma)):
+        raise ValueError(f"loss_weighting_gamma={gamma!r} must be a finite number > 0")
+    if not (k > 0 and np.isfinite(k)):
+        raise ValueError(f"loss_weighting_k={k!r} must be a finite number > 0")
+    if scheme != "table":
+        if table is not None:
+            raise ValueError(f"loss_weighting_table is given but loss_weighting is '{scheme}', not 'table'")
+        return scheme, gamma, k, None
+    if table is None:
+        raise ValueError("loss_weighting='table' needs loss_weighting_table (one weight per timestep)")
+    table = np.asarray(torch.as_tensor(table).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+    if table.shape[0] != h.num_timesteps:
+        raise ValueError(f"loss_weighting_table has {table.shape[0]} entries, the schedule {h.num_timesteps} timesteps")
+    if not (np.abs(table) <= np.finfo(np.float32).max).all() or (table < 0).any():          # (NaN fails the comparison)
+        raise ValueError("loss_weighting_table must hold finite (in fp32), non-negative weights")
+    return scheme, gamma, k, table
+
+
+def loss_weight_table(alphas_cumprod_fp32, parameterization, scheme, gamma=5.0, k=1.0):
+    """[T] fp32 weights on the loss of the TRAINED target.  Each scheme is a weight omega(SNR) on the x0 error,
+    SNR = ac / (1 - ac): 'min_snr' min(SNR, gamma) (Hang et al. 2023), 'trunc_snr' max(SNR, 1) (Salimans & Ho 2022), 'p2'
+    SNR / (k + SNR)^gamma (Choi et al. 2022), carried to the target by ||d eps||^2 = SNR ||d x0||^2 and ||d v||^2 =
+    (SNR + 1) ||d x0||^2: 'x0' omega, 'eps' omega / SNR, 'v' omega / (SNR + 1), each quotient written so that it is finite
+    at SNR == 0.  float64 math from the fp32 ``alphas_cumprod`` buffer (as ``DPMSolverSampler.plan``), rounded once."""
+    if parameterization not in ("eps", "x0", "v"):
+        raise NotImplementedError(f"parameterization '{parameterization}'")
+    if not gamma > 0 or not k > 0:
+        raise ValueError(f"loss weighting: gamma={gamma!r} and k={k!r} must be > 0")
+    a = torch.as_tensor(alphas_cumprod_fp32).detach().float().cpu().double().numpy()
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        snr = a / (1.0 - a)
+        if scheme == "min_snr":
+            w = np.minimum(1.0, gamma / snr) if parameterization == "eps" else np.minimum(snr, gamma)
+        elif scheme == "trunc_snr":
+            if parameterization == "eps" and (snr == 0).any():
+                raise ValueError("loss_weighting='trunc_snr' on 'eps' is max(1, 1 / SNR): infinite where alphas_cumprod is 0")
+            w = np.maximum(1.0, 1.0 / snr) if parameterization == "eps" else np.maximum(snr, 1.0)
+        elif scheme == "p2":
+            w = (k + snr) ** -gamma if parameterization == "eps" else snr / (k + snr) ** gamma
+        else:
+            raise ValueError(f"loss_weighting={scheme!r}: one of {LOSS_WEIGHTINGS[:-1]} has a formula")
+        if parameterization == "v":
+            w = w / (snr + 1.0)
+    w = torch.tensor(w, dtype=torch.float64).float()
+    if not torch.isfinite(w).all():
+        raise ValueError(f"loss_weighting='{scheme}' on '{parameterization}': the weight table is not finite "
+                         f"(alphas_cumprod reaches {float(a.max())!r})")
+    return w
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=False, timestep_spacing="leading"):
@@ -721,6 +794,8 @@ class Schedule_DDPM(nn.Module):
         if self.zero_terminal_snr and h.parameterization == "eps":
             raise ValueError("zero_terminal_snr with parameterization='eps': at SNR 0 the input is the noise, so the target "
                              "carries no information; use 'v' (or 'x0')")
+        # optional hparams (not in the reference): per-timestep loss weights, buffer ``loss_weights`` (sgdm_amd/train.py)
+        self.loss_weighting = loss_weighting_option(h)
         self.register_schedule(given_betas=h.given_betas, beta_schedule=h.beta_schedule, timesteps=h.num_timesteps,
                                linear_start=h.linear_start, linear_end=h.linear_end, cosine_s=h.cosine_s)
 
@@ -771,6 +846,11 @@ class Schedule_DDPM(nn.Module):
         lvlb[0] = lvlb[1]
         reg("lvlb_weights", lvlb, persistent=False)
         assert not torch.isnan(self.lvlb_weights).all()
+        if self.loss_weighting is not None:
+            scheme, gamma, k, table = self.loss_weighting
+            lw = (torch.tensor(table, dtype=torch.float64).float() if scheme == "table" else
+                  loss_weight_table(self.alphas_cumprod, h.parameterization, scheme, gamma, k))
+            reg("loss_weights", lw.to(dev), persistent=False)
         reg("snr_derivative", torch.zeros(1000, dtype=torch.float32).to(dev))
         reg("SNR", torch.zeros(1000, dtype=torch.float32).to(dev))
         # host copies of the per-step scalars of the fused step kernel (fp32 math as on the device)

@@ -13,7 +13,9 @@ walking the forward tape in reverse:
   * GroupNorm(+FiLM)+SiLU backward = ``sgd_gn_bwd_reduce/coef/apply`` (resample adjoints of the up/down
     ResBlocks and the identity-skip gradient folded into the apply pass);
   * attention backward = ``sgd_attention_bwd`` with the forward's log-sum-exp (no score matrix stored);
-  * q_sample / MSE loss = ``sgd_q_sample`` / ``sgd_mse_loss``.
+  * q_sample / MSE loss = ``sgd_q_sample`` / ``sgd_mse_loss``;
+  * with the hparam ``loss_weighting`` (not in the reference): the per-timestep weighted loss and its gradient =
+    ``sgd_loss_fwd`` / ``sgd_loss_bwd`` (``_WeightedLossFn``), the target formed on the fly.
 
 ``loss.backward()`` works because the UNet evaluation is a ``torch.autograd.Function`` whose inputs are the
 trainable parameters; it returns one gradient tensor per parameter in the reference layout.
@@ -1017,6 +1019,40 @@ class _MSEFn(torch.autograd.Function):
         return (-2.0 / chw) * (target - eps) * gper.reshape(B, 1, 1, 1), None
 
 
+_LOSS_PAR = {"eps": 0, "x0": 1, "v": 2}           # include/sgdm_hip.h: sgd_loss_fwd's par / kind
+_LOSS_KIND = {"l2": 0, "l1": 1, "huber": 2}
+
+
+class _WeightedLossFn(torch.autograd.Function):
+    """(per_w, per_raw) = per-sample loss of the trained target with and without the timestep weight wt[t], one launch
+    (sgd_loss_fwd); the gradient for the model output in one more (sgd_loss_bwd).  The target -- noise, x_start or
+    sa[t] * noise - s1[t] * x_start -- is formed inside both kernels from the tensors q_sample read: none is written."""
+
+    @staticmethod
+    def forward(ctx, out, x0, noise, t, sa, s1, wt, par, kind):
+        lib = L.load()
+        out = out.contiguous().float()
+        B, chw = out.shape[0], out[0].numel()
+        per_raw, per_w = (torch.empty(B, dtype=torch.float32, device=out.device) for _ in range(2))
+        L.check(lib.sgd_loss_fwd(_ptr(out), _ptr(x0), _ptr(noise), _ptr(t), _ptr(sa), _ptr(s1), _ptr(wt), par, kind, B, chw,
+                                 _ptr(per_raw), _ptr(per_w), torch.cuda.current_stream().cuda_stream), "sgd_loss_fwd")
+        ctx.save_for_backward(out, x0, noise, t, sa, s1, wt)
+        ctx.par, ctx.kind = par, kind
+        ctx.mark_non_differentiable(per_raw)
+        return per_w, per_raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, _graw):
+        out, x0, noise, t, sa, s1, wt = ctx.saved_tensors
+        gper = gper.contiguous().float()
+        gout = torch.empty_like(out)
+        L.check(L.load().sgd_loss_bwd(_ptr(out), _ptr(x0), _ptr(noise), _ptr(t), _ptr(sa), _ptr(s1), _ptr(wt), gper.data_ptr(),
+                                      1.0, ctx.par, ctx.kind, out.shape[0], out[0].numel(), _ptr(gout),
+                                      torch.cuda.current_stream().cuda_stream), "sgd_loss_bwd")
+        return (gout,) + (None,) * 8
+
+
 def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     """LatentDiffusion.p_losses (ddpm.py:54-86)"""
     fn = getattr(diff.denoise_fn, "__self__", diff.denoise_fn)        # the UNet (a bound forward or the module itself)
@@ -1029,11 +1065,17 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     if h.parameterization not in ("eps", "x0", "v"):
         raise NotImplementedError()
     v_target = None                     # parameterization 'v' (Salimans & Ho 2022): sa[t] * noise - s1[t] * x_start
+    # hparam loss_weighting (diffusion.loss_weight_table): per-timestep weights on the per-sample loss; on the device the
+    # loss and its gradient are then two kernels that form the target themselves (no v_target, no torch op chain)
+    weights = s.loss_weights if getattr(s, "loss_weighting", None) is not None else None
+    fused = weights is not None and x_start.device.type == "cuda"
+    if fused and h.loss_type not in _LOSS_KIND:
+        raise NotImplementedError(f"unknown loss type '{h.loss_type}'")
     if x_start.device.type == "cuda":
         x_noisy = torch.empty_like(x_start)
         B = x_start.shape[0]
         x0, nz, tt = x_start.contiguous().float(), noise.contiguous().float(), t.contiguous().to(torch.int64)
-        if h.parameterization == "v":   # x_noisy and the target from one read of x_start and noise
+        if h.parameterization == "v" and not fused:   # x_noisy and the target from one read of x_start and noise
             v_target = torch.empty_like(x_start)
             L.check(lib.sgd_q_sample_v(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
                                        _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy), _ptr(v_target),
@@ -1056,7 +1098,11 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
         target = noise
     else:
         target = v_target
-    if h.loss_type == "l2":
+    raw = None                          # the unweighted per-sample loss when weighting is on
+    if fused:
+        loss, raw = _WeightedLossFn.apply(model_output, x0, nz, tt, s.sqrt_alphas_cumprod, s.sqrt_one_minus_alphas_cumprod,
+                                          weights, _LOSS_PAR[h.parameterization], _LOSS_KIND[h.loss_type])
+    elif h.loss_type == "l2":
         loss = _MSEFn.apply(model_output, target)
     elif h.loss_type == "l1":
         loss = (target - model_output).abs().reshape(len(target), -1).mean(1)
@@ -1064,11 +1110,15 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
         loss = torch.nn.functional.smooth_l1_loss(target, model_output, reduction="none").reshape(len(target), -1).mean(1)
     else:
         raise NotImplementedError(f"unknown loss type '{h.loss_type}'")
-    if prefix == "train":
-        loss_dict[f"{prefix}/epoch_stats_y"] = loss.detach()
+    if weights is not None and raw is None:                                   # CPU: the same weights on the torch chain
+        raw, loss = loss.detach(), loss * weights[t]
+    if prefix == "train":               # (the UNWEIGHTED per-sample loss: logged per-timestep curves stay comparable)
+        loss_dict[f"{prefix}/epoch_stats_y"] = loss.detach() if raw is None else raw
         loss_dict[f"{prefix}/epoch_stats_x"] = t.detach()
     loss = loss.mean()
     loss_dict[f"{prefix}/ddpm_loss"] = loss.detach()
+    if raw is not None:
+        loss_dict[f"{prefix}/ddpm_loss_raw"] = raw.mean()
     loss = loss + loss_inside
     loss_dict[f"{prefix}/loss"] = loss.detach()
     return loss, loss_dict
