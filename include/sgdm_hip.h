@@ -175,6 +175,34 @@ int sgd_igemm_stats_parts(const sgd_igemm_args* args /* HOST pointer */);
  * the caller keeps the direct SGD_RS_UP2 launch.  cin_p / cout_p / pointers are not read. */
 int sgd_igemm_subpixel_ok(const sgd_igemm_args* args /* HOST pointer */);
 
+/* Second input of a fused launch (sgd_igemm_fused_aux): the virtual channel concat x0 | x1 of two NHWC maps of the OUTPUT's
+ * n x ho x wo pixels, c0 and c1 channels (multiples of 32; c1 = 0: x0 alone). */
+typedef struct sgd_igemm_aux {
+    const float* x0;
+    const float* x1;
+    int32_t c0, c1;
+} sgd_igemm_aux;
+/* A ResBlock's 3x3 out conv and its 1x1 skip conv as ONE GEMM over K = 9 * cin + (aux->c0 + aux->c1):
+ *   y = conv3x3(act(x)) + conv1x1(aux->x0 | aux->x1) + bias,
+ * the 1x1 product accumulated in the 3x3 conv's accumulators (extra K steps behind the tile's last tap: the aux input is read raw,
+ * centre tap only).  `args` describes the 3x3 conv exactly as for sgd_igemm, except that
+ *   - args->w holds the 3x3 weights packed with ksize 3 and, directly behind them (sgd_packed_weight_bytes(cout, cin, 3, prec)
+ *     bytes further), the 1x1 weights [cout, aux->c0 + aux->c1] packed with ksize 1, BOTH with the scale of ONE amax folded over
+ *     both tensors (sgd_weight_amax twice into one zeroed word, sgd_pack_weight_scaled twice with it): *args->w_scale_inv
+ *     scales the shared accumulators;
+ *   - args->bias is the SUM of the two convs' biases (or NULL), args->res is NULL.
+ * Statistics, the balanced tail (the aux K steps belong to the tile's last K part) and args->grid_cap work as for sgd_igemm.
+ * SGD_ERR_ARG unless sgd_igemm_fused_aux_ok(args, aux). */
+int sgd_igemm_fused_aux(const sgd_igemm_args* args /* HOST */, const sgd_igemm_aux* aux /* HOST */, void* stream);
+/* 1 if sgd_igemm_fused_aux serves this pair, 0 otherwise (the caller then launches the two convs: sgd_igemm twice, the first
+ * one's output as the second one's residual).  Host only -- no device, no launch, no error state.  It refuses: arithmetic modes
+ * other than SGD_PREC_F16X3 / SGD_PREC_BF16X3; anything but a stride-1 3x3 conv without resampling whose input is GroupNorm
+ * coefficients + SiLU (SGD_PRO_AFFINE_NC, pro_silu) over whole 32-channel chunks and whose tiles hold 128 pixels of one image
+ * (output maps of at least 128 pixels); drop_p > 0; a residual; aux channel counts that are not multiples of 32; launches for
+ * which sgd_igemm would not take the 128-column tile (cout % 128 != 0, the small-launch rule's 32-column tile, the 128 x 256
+ * tile); SGD_TUNE_DEFER.  Pointers and cin_p / cout_p are not read. */
+int sgd_igemm_fused_aux_ok(const sgd_igemm_args* args /* HOST */, const sgd_igemm_aux* aux /* HOST */);
+
 /* bytes of the packed weight buffer for given dims; w_src is [cout, cin, k, k] (OIHW) or [cout, cin] */
 int64_t sgd_packed_weight_bytes(int32_t cout, int32_t cin, int32_t ksize, int32_t prec);
 int sgd_pack_weight(const float* w_src, void* w_dst, int32_t cout, int32_t cin, int32_t ksize,

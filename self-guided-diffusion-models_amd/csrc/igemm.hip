@@ -335,7 +335,7 @@ __device__ __forceinline__ Tile tile_at(const Geo& g, int lin, int bn, int tw, i
 // One block of the persistent grid: the compile-time shape of an instance, the run-time schedule of this block, and the two
 // wave roles as member functions -- the kernel itself (below) only carves up LDS, builds the first tile tables and hands the
 // waves their role.  (Round 6: the 1,350-line kernel body cut into units; the ISA of all 25 instances is unchanged.)
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER>
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER, bool AUX = false>
 struct IgemmBlock {
     // ------------------------------------------------------------------------------------------ compile-time shape
     // TAPS = 4: the sub-pixel conv (SGD_RS_UP2_SUBPIXEL) -- a stride-1 3x3 halo at the input resolution, 2x2 taps placed by
@@ -379,10 +379,16 @@ struct IgemmBlock {
     static constexpr int STG_LD = BN + 4;
     static_assert(!DEFER || (BN == 128 && TAPS == 9 && VEC && !M16), "loader-side epilogue: 3x3, 128-column tiles");
     static_assert(!SUBPIX || (VEC && PREC != SGD_PREC_F32 && BN >= 128), "sub-pixel conv: 16-byte inputs, split modes, 128-column tiles");
+    // AUX (sgd_igemm_fused_aux): behind a tile's nchunks x 9 K steps, one K step per 32-channel chunk of a SECOND input (x.x0 | x.x1,
+    // raw, centre tap) into the same accumulators -- a ResBlock's 1x1 skip conv inside its 3x3 out conv.  The weight stream is
+    // linear in units ([chunk][tap][block], then [aux chunk][block]); of a K-split tile the aux steps belong to the LAST part
+    // (cend == nchunks: the finisher), so tail_split and the slab layout count main chunks only, as without AUX.
+    static_assert(!AUX || (BN == 128 && TAPS == 9 && VEC && M16), "fused aux input: 3x3, 128-column tiles, 16x16x32 form");
 
     // ------------------------------------------------------------------------------------------ run-time state of the block
     const sgd_igemm_args& a;
     const Geo& g;
+    const sgd_igemm_aux& x;       // AUX only
     float* As;                    // [NA][pix][LDA]
     int2* pixtab;                 // [4][pix] (source row or -1, image n)
     float* bias_s;                // [cout_p]
@@ -540,14 +546,15 @@ struct IgemmBlock {
     __device__ __forceinline__ void epilogue(const AccV (&acc)[RB][CBN], const Tile& T, int wm, int wn, int lane_e, int cb, float wsk,
                                              const char* part_base, int nparts) const;
     __device__ __forceinline__ void loader_role();
+    __device__ __forceinline__ void loader_role_aux();
     __device__ __forceinline__ void compute_role();
 };
 
 // =========================================================================================
 // loader role (waves 4-7)
 // =========================================================================================
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER>
-__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_role() {
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER, bool AUX>
+__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::loader_role() {
     PROBE_BEGIN();
     // The loader shares its SIMD's vector issue with an MFMA wave that always has an instruction waiting; at equal
     // priority the older (MFMA) wave wins every arbitration and the loader got ~1 issue slot per MFMA (measured: ~460
@@ -734,6 +741,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
                 };
                 f32x4 araw[AJ][NS];
                 Coef kq;
+                // (loader_role_aux below carries a copy of this transform and of the row table / coefficient loads for the fused
+                // instance's main chunks -- kept apart so that this loader's instruction stream stays what it was: change both)
                 auto transform = [&](f32x4 v, bool ok) __attribute__((always_inline)) {
                     if (ABL(256)) return v;
                     if constexpr (uni) {
@@ -1185,11 +1194,168 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::loader_r
 }
 
 // =========================================================================================
+// loader role of the AUX instance (sgd_igemm_fused_aux; waves 4-7)
+// =========================================================================================
+// The lean conv loader above (GroupNorm affine + SiLU instantiation) written as a walk over the block's chunk STREAM -- per tile
+// its main chunks, then (whole tiles and finishers: cend == nchunks) naux aux chunks -- instead of over periods: chunk i of the
+// stream goes to ring slot i % NA two periods before the compute waves reach it, one barrier per chunk, as there.
+//   main chunk: the 180-pixel halo tile, 6 items per thread, transformed; its raw rows are requested while the chunk before it is
+//               staged (a whole 9-step period earlier).
+//   aux chunk:  ONE K step on the compute side, so it is staged as the 1x1 loader stages a step: the 128 centre pixels only
+//               (4 items per thread), raw -- no transform, no padding -- through a 3-deep register ring (an aux period is one MFMA
+//               step, ~0.6 us: a request has to be three of them old to have landed), written to the halo positions the centre
+//               tap reads (pixel (ty + 1, tx + 1) of the slot): the compute waves keep their fragment addresses and the
+//               conflict-free lane map of tap (1, 1); the other 52 pixels of the slot are not read by an aux step.
+// The switch is wave-uniform and happens once per tile: with the tile's last main chunk the first three aux chunks are requested
+// -- and, in the main registers, the NEXT tile's first chunk, whose rows then have the whole aux phase to land.
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER, bool AUX>
+__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::loader_role_aux() {
+    if constexpr (AUX) {
+        PROBE_BEGIN();
+        __builtin_amdgcn_s_setprio(2);
+        constexpr int LT = A_THREADS;
+        constexpr int AJ = (FAST_PIX * 8 + LT - 1) / LT;         // main items per thread per chunk (6)
+        constexpr int AX = BM * 8 / LT;                          // aux items per thread per chunk (4)
+        typedef std::integral_constant<int, 0> R0;
+        typedef std::integral_constant<int, 1> R1;
+        typedef std::integral_constant<int, 2> R2;
+        const int lt = tid - NCOMP;
+        const int c4 = lt & 7;                                   // channel quad (main and aux alike: LT % 8 == 0)
+        const int items = g.pix * 8;
+        const int naux = (x.c0 + x.c1) / KC;
+        // ---- main items: halo pixel, source row (per tile), padding flag -- as the lean loader
+        int pixj[AJ], rows2[AJ];
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) {
+            const int idx = lt + j * LT;
+            pixj[j] = (idx < items ? idx : items - 1) >> 3;      // slots past the tile: duplicates of its last pixel
+        }
+        unsigned valid = 0;
+        auto load_rows = [&](int k) __attribute__((always_inline)) {
+            const int2* tab = pixtab + (size_t)(k & 3) * g.pix;
+            valid = 0;
+#pragma unroll
+            for (int j = 0; j < AJ; ++j) {
+                const int ex = tab[pixj[j]].x;
+                rows2[j] = ex < 0 ? 0 : ex;
+                if (ex >= 0) valid |= 1u << j;
+            }
+        };
+        // ---- aux items: tile pixel p = lt / 8 + 32 j -> float offset of its halo position in a slot, source row relative to the
+        // tile's first pixel (the tile lies inside one image: g.nb == 1, and the aux maps have the output's n x ho x wo pixels)
+        int apix[AX], arel[AX];
+#pragma unroll
+        for (int j = 0; j < AX; ++j) {
+            const int p = (lt >> 3) + j * (LT / 8);
+            const int tx = p & (TW - 1), ty = p >> g.tw_l2;
+            apix[j] = ((ty + 1) * g.hw + tx + 1) * LDA;
+            arel[j] = ty * a.wo + tx;
+        }
+        f32x4 araw[AJ], xraw[NB_RING][AX];
+        Coef kq;
+        auto request_main = [&](int img0, int chunk) __attribute__((always_inline)) {
+            const int ch = chunk * KC;
+            const float* src;
+            int stride;
+            if (ch < a.c0) { src = a.x0 + ch; stride = a.c0; }
+            else { src = a.x1 + (ch - a.c0); stride = a.c1; }
+            const long ko = (long)img0 * cin + ch + c4 * 4;
+            kq.p = ld4(a.pa + ko);
+            kq.q = ld4(a.pb + ko);
+#pragma unroll
+            for (int j = 0; j < AJ; ++j) araw[j] = ld4(src + (long)rows2[j] * stride + c4 * 4);
+        };
+        auto finish_main = [&](int slot) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < AJ; ++j) {
+                // SiLU with the padding mask folded into the denominator (see the lean loader's transform)
+                const float den = ((valid >> j) & 1u) ? 1.0f : __builtin_inff();
+                f32x4 v = araw[j] * kq.p + kq.q;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] * __builtin_amdgcn_rcpf(den + __expf(-v[e]));
+                lds_store_act<PREC>(As + (size_t)slot * a_floats + (size_t)pixj[j] * LDA, c4, v);
+            }
+        };
+        // aux chunk i of the tile whose first pixel is source row arow0 -> register set R; chunks past the last one are clamped
+        // duplicates (harmless loads that nobody stages) instead of a branch around the loads
+        auto request_aux = [&](auto rc, int i, int arow0) __attribute__((always_inline)) {
+            constexpr int R = decltype(rc)::value;
+            const int ch = (i < naux ? i : naux - 1) * KC;
+            const float* src;
+            int stride;
+            if (ch < x.c0) { src = x.x0 + ch; stride = x.c0; }
+            else { src = x.x1 + (ch - x.c0); stride = x.c1; }
+#pragma unroll
+            for (int j = 0; j < AX; ++j) xraw[R][j] = ld4(src + (long)(arow0 + arel[j]) * stride + c4 * 4);
+        };
+        auto finish_aux = [&](auto rc, int slot) __attribute__((always_inline)) {
+            constexpr int R = decltype(rc)::value;
+#pragma unroll
+            for (int j = 0; j < AX; ++j) lds_store_act<PREC>(As + (size_t)slot * a_floats + apix[j], c4, xraw[R][j]);
+        };
+
+        Tile T = tile_at<SUBPIX>(g, lin_of(0), BN, TW, TH);
+        load_rows(0);
+        request_main(T.img0, cbeg(0));
+        int slot = 0;                                            // ring slot of the next chunk of the stream
+        for (int k = 0; k < ntiles; ++k) {
+            const int c_beg = cbeg(k), c_end = cend(k);
+            const bool haux = c_end == nchunks;
+            const int img0 = T.img0;
+            const int arow0 = (T.img0 * a.ho + T.ty0) * a.wo + T.tx0;
+            for (int c = c_beg; c < c_end; ++c) {
+                finish_main(slot);
+                if (c + 1 < c_end) {
+                    request_main(img0, c + 1);
+                } else if (haux) {
+                    request_aux(R0(), 0, arow0);
+                    request_aux(R1(), 1, arow0);
+                    request_aux(R2(), 2, arow0);
+                    if (k + 1 < ntiles) {
+                        // the next tile's rows and first chunk; its table slot k & 3 was read when THIS tile opened (>= 3 barriers
+                        // ago) and holds tile k + 4 from here on
+                        T = tile_at<SUBPIX>(g, lin_of(k + 1), BN, TW, TH);
+                        load_rows(k + 1);
+                        request_main(T.img0, cbeg(k + 1));
+                        build_pixtab(k + 4, lt, LT);
+                    }
+                }
+                slot = slot + 1 == NA ? 0 : slot + 1;
+                // barrier 0 stands behind the stream's first TWO chunks: the compute waves' prefetch runs into the second
+                if (k > 0 || c > c_beg) SYNC();
+            }
+            if (haux) {
+                auto step = [&](auto rc, int i) __attribute__((always_inline)) {
+                    finish_aux(rc, slot);
+                    request_aux(rc, i + NB_RING, arow0);
+                    slot = slot + 1 == NA ? 0 : slot + 1;
+                    SYNC();
+                };
+                int i = 0;
+                for (; i + 3 <= naux; i += 3) {
+                    step(R0(), i);
+                    step(R1(), i + 1);
+                    step(R2(), i + 2);
+                }
+                if (i < naux) {
+                    step(R0(), i);
+                    if (i + 1 < naux) step(R1(), i + 1);
+                }
+            }
+        }
+        // the compute waves are two chunks behind
+        SYNC();
+        SYNC();
+        PROBE_END(1);
+    }
+}
+
+// =========================================================================================
 // epilogue of a tile (compute waves)
 // =========================================================================================
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER>
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER, bool AUX>
 template <int RES, bool PART>
-__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::epilogue(const AccV (&acc)[RB][CBN], const Tile& T, int wm, int wn,
+__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::epilogue(const AccV (&acc)[RB][CBN], const Tile& T, int wm, int wn,
                                                                                  int lane_e, int cb, float wsk, const char* part_base,
                                                                                  int nparts) const {
     const int li = lane & 31;
@@ -1365,8 +1531,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::epilogue
     }
 }
 
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER>
-__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_role() {
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER, bool AUX>
+__device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::compute_role() {
     PROBE_BEGIN();
     // =========================================================================================
     // compute role
@@ -1537,7 +1703,15 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
             const float* acur = As + (size_t)aslot * a_floats + pcur;
             const float* anext = As + (size_t)naslot * a_floats + (chunk + 1 == c_end ? pnext : pcur);
             // step after this chunk's last one: next chunk, next tile, or (end of the stream) the same slice again
-            const char* const wlast = chunk + 1 == c_end ? (wseam ? wseam : wp + (TAPS - 1) * wstep) : nullptr;
+            const char* wlast = chunk + 1 == c_end ? (wseam ? wseam : wp + (TAPS - 1) * wstep) : nullptr;
+            if constexpr (AUX) {
+                // the tile's aux steps follow its last main chunk (of a K-split tile: the finisher's): the prefetches of the last tap
+                // run into the CENTRE tap of the first aux chunk, the weight stream simply goes on
+                if (chunk + 1 == c_end && c_end == nchunks) {
+                    anext = As + (size_t)naslot * a_floats + rowstep + LDA;
+                    wlast = nullptr;
+                }
+            }
             // taps fully unrolled: tap offsets are compile-time, so no scalar index math sits between the MFMA blocks
             static_for<TAPS>([&](auto tapc) {
                 constexpr int tap = decltype(tapc)::value;
@@ -1547,6 +1721,23 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
                 wp = wnext;
             });
             aslot = naslot;
+        }
+        if constexpr (AUX) {
+            // aux steps: ONE K step per 32-channel chunk of the second input, staged by the loaders at the centre-tap positions of a
+            // ring slot (loader_role_aux), so the fragment addresses are those of tap (1, 1) and every step is a chunk seam: its
+            // prefetches read the next slot -- the next aux chunk's centre tap, or tap (0, 0) of the next tile's first chunk
+            if (c_end == nchunks) {
+                const int naux = (x.c0 + x.c1) / KC;
+                for (int ax = 0; ax < naux; ++ax) {
+                    const int naslot = aslot + 1 == NA ? 0 : aslot + 1;
+                    const bool lastx = ax + 1 == naux;
+                    const float* nfrag = As + (size_t)naslot * a_floats + (lastx ? pnext : rowstep + LDA);
+                    const char* wnext = lastx ? (wseam ? wseam : wp) : wp + wstep;
+                    do_step(nfrag, nfrag, std::integral_constant<int, TAPS - 1>(), std::integral_constant<int, 0>(), wnext);
+                    wp = wnext;
+                    aslot = naslot;
+                }
+            }
         }
         if constexpr (DEFER) {
             if (k + 1 < ntiles) {
@@ -1587,6 +1778,14 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
                 // PRODUCER (R1 of the guide's publish recipe): write-through (sc1) 16-byte stores -- no release fence, no
                 // write-back of the L2's other dirty lines --, every storing wave drains its stores, then signals for itself
                 __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slab0 + (size_t)rem_part * SLAB, 0, (int)SLAB, 0x00020000);
+                int ptid = tid;
+                if constexpr (AUX) {
+                    // (the thread index re-read from the hardware, as the finisher does: with the aux loop's live values it was the
+                    // one register the allocator spilled across the K loop, and a kernel with any scratch pays for it per launch)
+                    int lane_p;
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_p));
+                    ptid = wave * 64 + lane_p;
+                }
 #pragma unroll
                 for (int mt = 0; mt < RB; ++mt)
 #pragma unroll
@@ -1594,7 +1793,7 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
 #pragma unroll
                         for (int q = 0; q < QPB; ++q)
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, accq(acc, mt, nt, q)), rs,
-                                                                   (((mt * CBN + nt) * QPB + q) * NCOMP + tid) * 16, 0, 16 /* sc1 */);
+                                                                   (((mt * CBN + nt) * QPB + q) * NCOMP + ptid) * 16, 0, 16 /* sc1 */);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;                                                     // no epilogue; the split tile is the block's last
@@ -1695,10 +1894,10 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER>::compute_
     PROBE_END(0);
 }
 
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER = false>
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER = false, bool AUX = false>
 __global__ __launch_bounds__(NTHREADS) void igemm_kernel(const KArgs ka) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    IgemmBlock<BN, PREC, VEC, TAPS, DEFER> blk{ka.a, ka.g};
+    IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX> blk{ka.a, ka.g, ka.x};
     if (!blk.init(smem)) return;
     blk.build_pixtab(0, blk.tid, NTHREADS);
     blk.build_pixtab(1, blk.tid, NTHREADS);
@@ -1708,15 +1907,19 @@ __global__ __launch_bounds__(NTHREADS) void igemm_kernel(const KArgs ka) {
     if (blk.bias_lds)
         for (int i = blk.tid; i < ka.a.cout_p; i += NTHREADS) blk.bias_s[i] = (ka.a.bias && i < ka.a.cout && !ABL(2)) ? ka.a.bias[i] : 0.f;
     __syncthreads();
-    if (blk.tid >= NCOMP) blk.loader_role();
-    else blk.compute_role();
+    if (blk.tid >= NCOMP) {
+        if constexpr (AUX) blk.loader_role_aux();
+        else blk.loader_role();
+    } else {
+        blk.compute_role();
+    }
 }
 
-template <int BN, int PREC, bool VEC, int TAPS, bool DEFER = false>
+template <int BN, int PREC, bool VEC, int TAPS, bool DEFER = false, bool AUX = false>
 int launch1(const KArgs& ka, size_t smem, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute((const void*)igemm_kernel<BN, PREC, VEC, TAPS, DEFER>,
+        (void)hipFuncSetAttribute((const void*)igemm_kernel<BN, PREC, VEC, TAPS, DEFER, AUX>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr = true;
     }
@@ -1729,7 +1932,7 @@ int launch1(const KArgs& ka, size_t smem, hipStream_t st) {
     int grid = ((total + 7) / 8) * 8;
     if (grid > full) grid = full;
     if (ka.a.work && total >= 8) grid = full;     // balanced tail: blocks without a whole tile take K parts of the last ones
-    hipLaunchKernelGGL((igemm_kernel<BN, PREC, VEC, TAPS, DEFER>), dim3(grid), dim3(NTHREADS), smem, st, ka);
+    hipLaunchKernelGGL((igemm_kernel<BN, PREC, VEC, TAPS, DEFER, AUX>), dim3(grid), dim3(NTHREADS), smem, st, ka);
     const int rc = sgd_check_launch();
     // a launch that did not start leaves nothing behind, but one that faulted may have left arrival counters half-way:
     // never hand such a head to the next launch
@@ -1737,11 +1940,20 @@ int launch1(const KArgs& ka, size_t smem, hipStream_t st) {
     return rc;
 }
 
-// vec: 0 scalar inputs, 1 16-byte inputs, 2 16-byte inputs + the loader-side epilogue (DEFER: 3x3, 128-column tiles, split modes)
+// vec: 0 scalar inputs, 1 16-byte inputs, 2 16-byte inputs + the loader-side epilogue (DEFER: 3x3, 128-column tiles, split modes),
+//      3 16-byte inputs + the fused aux input (AUX: 3x3, 128-column tiles, f16x3 / bf16x3; sgd_igemm_fused_aux)
 // taps: 9 conv, 4 sub-pixel conv, 1 flat (one 32-channel plane per barrier), 2 flat with two planes per chunk (lean 16-byte launches)
 template <int BN, int PREC>
 int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
     const bool conv = taps == 9;
+    if (vec == 3) {
+#ifndef SGDM_IGEMM_NOPK
+        if constexpr (BN == 128 && (PREC == SGD_PREC_F16X3 || PREC == SGD_PREC_BF16X3)) {
+            if (conv) return launch1<BN, PREC, true, 9, false, true>(ka, smem, st);
+        }
+#endif
+        return SGD_ERR_ARG;
+    }
 #ifdef SGDM_IGEMM_NOPK
     if (taps == 4) return SGD_ERR_ARG;
     // the unit compiled without packed-f32 code generation (see the end of this file) serves the 1x1 / linear launches with
@@ -1782,9 +1994,12 @@ int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
 #error "igemm.hip is compiled once per arithmetic mode: -DSGDM_IGEMM_PREC=0..4 (build.py); geometry and entry points: igemm_host.hip"
 #endif
 #ifdef SGDM_DEV_ONE      /* development: compile ONE kernel instance (register / asm inspection), never linked */
+#ifndef SGDM_DEV_AUX
+#define SGDM_DEV_AUX false
+#endif
 #define SGD_DISPATCH_BODY(P)                                                                                        \
     const KArgs& ka = *reinterpret_cast<const KArgs*>(kap); (void)bn; (void)vec; (void)taps;                         \
-    return launch1<SGDM_DEV_BN, P, true, SGDM_DEV_ONE, SGDM_DEV_DEFER>(ka, smem, st);
+    return launch1<SGDM_DEV_BN, P, true, SGDM_DEV_ONE, SGDM_DEV_DEFER, SGDM_DEV_AUX>(ka, smem, st);
 #else
 #define SGD_DISPATCH_BODY(P)                                                                                        \
     const KArgs& ka = *reinterpret_cast<const KArgs*>(kap);                                                         \

@@ -1,5 +1,5 @@
 // Host side of the fused implicit-GEMM conv / linear kernel (csrc/igemm.hip): launch geometry, tile / instance rules, the balanced
-// tail's workspace layout hook and the extern "C" entry points sgd_igemm / sgd_igemm_stats_parts / sgd_igemm_work_* of
+// tail's workspace layout hook and the extern "C" entry points sgd_igemm / sgd_igemm_fused_aux / sgd_igemm_stats_parts / sgd_igemm_work_* of
 // include/sgdm_hip.h.  The kernel instances live in one translation unit per arithmetic mode (igemm.hip) and are reached through
 // the sgd_igemm_dispatch_* functions declared in igemm_shared.h; the argument block crosses as bytes.
 #include <stdint.h>
@@ -179,11 +179,49 @@ static bool subpixel_ok(const sgd_igemm_args& a0) {
 
 extern "C" int sgd_igemm_subpixel_ok(const sgd_igemm_args* args) { return args && subpixel_ok(*args) ? 1 : 0; }
 
-extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
+// Fused 3x3 + 1x1 rule (include/sgdm_hip.h: sgd_igemm_fused_aux_ok): the ONE place that decides whether a ResBlock's out conv
+// takes its skip conv's input as extra K steps (igemm_kernel<128, .., TAPS = 9, AUX>); Python asks it instead of repeating the
+// bounds.  Everything the instance is NOT built for is refused here: it exists for the lean-loader geometry only.
+static bool fused_aux_ok(const sgd_igemm_args& a, const sgd_igemm_aux& x) {
+    if (a.prec != SGD_PREC_F16X3 && a.prec != SGD_PREC_BF16X3) return false;            // the modes that carry the instance
+    if (a.mode != SGD_MODE_CONV3 || a.stride != 1 || a.resample != SGD_RS_NONE) return false;
+    if (a.pro != SGD_PRO_AFFINE_NC || !a.pro_silu || a.drop_p != 0.f || a.res) return false;
+    if (a.tune & SGD_TUNE_DEFER) return false;
+    const int cin = a.c0 + a.c1;
+    if (a.c0 <= 0 || a.c1 < 0 || cin % KC != 0 || (a.c1 > 0 && a.c0 % KC != 0)) return false;
+    if (x.c0 <= 0 || x.c1 < 0 || x.c0 % KC != 0 || x.c1 % KC != 0) return false;
+    if (a.cout <= 0 || a.y_ld < a.cout || ((a.cout | a.y_ld) & 3)) return false;
+    // the tile sgd_igemm itself would take for the 3x3 conv: 128 columns, neither the small-launch rule's 32 nor 128 x 256
+    if (column_tile(a) != 128) return false;
+    sgd_igemm_args b = a;
+    b.cout_p = a.cout;                                                                  // (cout % 128 == 0 here)
+    if (b.cout_p % 256 == 0 && want_bn256(b)) return false;
+    Geo g;
+    int na;
+    if (make_geo(a, g, 128, na) != SGD_OK) return false;
+    // lean-loader geometry: one image per tile, 128 output pixels, the split-phase halo tile
+    if (g.nb != 1 || !g.fast_a || (1 << (g.tw_l2 + g.th_l2)) != BM) return false;
+    if (a.stats && g.sparts == 0) return false;
+    const size_t smem = (size_t)na * g.pix * LDA * sizeof(float) + (size_t)g.pix * 32
+                        + (a.cout <= BIAS_LDS_MAX ? (size_t)a.cout * sizeof(float) : 0);
+    return smem <= 160 * 1024;
+}
+
+extern "C" int sgd_igemm_fused_aux_ok(const sgd_igemm_args* args, const sgd_igemm_aux* aux) {
+    return args && aux && fused_aux_ok(*args, *aux) ? 1 : 0;
+}
+
+// sgd_igemm (aux == nullptr) and sgd_igemm_fused_aux
+static int igemm_run(const sgd_igemm_args* args, const sgd_igemm_aux* aux, void* stream) {
     SGD_CLEAR_ERR();
     if (!args) return SGD_ERR_ARG;
     KArgs ka;
     ka.a = *args;
+    ka.x = sgd_igemm_aux{nullptr, nullptr, 0, 0};
+    if (aux) {
+        if (!fused_aux_ok(*args, *aux) || !aux->x0 || (aux->c1 > 0 && !aux->x1)) return SGD_ERR_ARG;
+        ka.x = *aux;
+    }
     sgd_igemm_args& a = ka.a;
     Geo& g = ka.g;
     if (!a.x0 || !a.w || !a.y || a.c0 <= 0 || a.c1 < 0 || a.cout <= 0) return SGD_ERR_ARG;
@@ -204,6 +242,7 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
     const bool sub = conv && a.resample == SGD_RS_UP2_SUBPIXEL;
     if (sub && !subpixel_ok(a)) return SGD_ERR_ARG;
     if (bn == 128 && a.cout_p % 256 == 0 && vec && (!a.res || a.res_mode == SGD_RS_NONE) && want_bn256(a)) bn = 256;
+    if (aux && (bn != 128 || !vec)) return SGD_ERR_ARG;          // (fused_aux_ok said 128 columns for cout_p = cout)
     int na;
     // Two planes per chunk (igemm_kernel<.., TAPS = 2>): OPT-IN, args.tune & SGD_TUNE_FLAT2.  Flat launches the lean loaders serve
     // (16-byte rows, no / per-image GroupNorm prologue, no dropout, whole 32-channel planes per source) with an even
@@ -274,6 +313,7 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
             smem_launch = smem_defer;
         }
     }
+    if (aux) variant = 3;
     switch (a.prec) {
         case SGD_PREC_F32: return sgd_igemm_dispatch_f32(&ka, bn, variant, taps, smem_launch, st);
         case SGD_PREC_F16X3: return ln_nopk ? sgd_igemm_dispatch_f16x3_nopk(&ka, bn, variant, taps, smem_launch, st)
@@ -286,4 +326,11 @@ extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) {
                                            : sgd_igemm_dispatch_bf16(&ka, bn, variant, taps, smem_launch, st);
         default: return SGD_ERR_ARG;
     }
+}
+
+extern "C" int sgd_igemm(const sgd_igemm_args* args, void* stream) { return igemm_run(args, nullptr, stream); }
+
+extern "C" int sgd_igemm_fused_aux(const sgd_igemm_args* args, const sgd_igemm_aux* aux, void* stream) {
+    if (!aux) return SGD_ERR_ARG;
+    return igemm_run(args, aux, stream);
 }

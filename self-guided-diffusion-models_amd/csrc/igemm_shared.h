@@ -77,6 +77,7 @@ struct Geo {
 struct KArgs {
     sgd_igemm_args a;
     Geo g;
+    sgd_igemm_aux x;          // second input of the fused launch (sgd_igemm_fused_aux); read by the AUX instance only
 };
 
 inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }

@@ -60,6 +60,11 @@ class IgemmArgs(C.Structure):
     ]
 
 
+class IgemmAux(C.Structure):
+    """mirror of ``struct sgd_igemm_aux`` (include/sgdm_hip.h): the second input of sgd_igemm_fused_aux"""
+    _fields_ = [("x0", vp), ("x1", vp), ("c0", i32), ("c1", i32)]
+
+
 class PackJob(C.Structure):
     """mirror of ``struct sgd_pack_job`` (include/sgdm_hip.h)"""
     _fields_ = [("src", vp), ("dst", vp), ("amax_bits", vp), ("scale_inv", vp), ("cout", i32), ("cin", i32), ("ksize", i32),
@@ -73,6 +78,8 @@ SIGNATURES = {
     "sgd_igemm": (i32, [C.POINTER(IgemmArgs), vp]),
     "sgd_igemm_stats_parts": (i32, [C.POINTER(IgemmArgs)]),
     "sgd_igemm_subpixel_ok": (i32, [C.POINTER(IgemmArgs)]),
+    "sgd_igemm_fused_aux": (i32, [C.POINTER(IgemmArgs), C.POINTER(IgemmAux), vp]),
+    "sgd_igemm_fused_aux_ok": (i32, [C.POINTER(IgemmArgs), C.POINTER(IgemmAux)]),
     "sgd_igemm_work_bytes": (i64, []),
     "sgd_igemm_work_status_offset": (i64, []),
     "sgd_igemm_tail_layout": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),

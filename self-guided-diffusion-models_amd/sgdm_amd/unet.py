@@ -192,6 +192,9 @@ class _Packed:
         self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=srcs[0].device)
         self.cin_p = self.cout_p = 0
         self.sig = None
+        # idle: a pack only the TRAINING forward launches (the pair of a fused ResBlock) while the engine prepares an inference
+        # evaluation -- refresh() leaves it stale until the next training forward (_Engine.refresh)
+        self.idle = False
         # split precisions: per-tensor power-of-two scale so hi AND lo halves stay in fp16's normal range whatever the
         # tensor's magnitude (include/sgdm_hip.h: sgd_igemm_args.w_scale_inv); formed on the device, no host round trip
         self.scaled = prec != L.PREC_F32
@@ -205,7 +208,7 @@ class _Packed:
 
     def refresh(self, stream):
         sig = tuple((s.data_ptr(), s._version) for s in self.srcs)
-        if sig == self.sig:
+        if sig == self.sig or self.idle:
             return
         lib = L.load()
         src = self.srcs[0].detach() if len(self.srcs) == 1 else torch.cat([s.detach() for s in self.srcs], 0)
@@ -233,6 +236,52 @@ class _Packed:
                                         C.byref(cin_p), C.byref(cout_p), stream), "sgd_pack_weight")
         self.cin_p, self.cout_p = cin_p.value, cout_p.value
         self._keep = src
+        self.sig = sig
+
+
+class _FusedPacked:
+    """A channel-changing ResBlock's out_layers.3 (3x3) and skip_connection (1x1) weights packed back to back for
+    sgd_igemm_fused_aux: the two products share their accumulators, so both tensors carry the scale of ONE amax folded over
+    both; the launch's bias is the sum of the two biases.  Follows all four parameters' versions; refreshed only in front of an
+    inference evaluation (the training forward launches the pair from their own packs)."""
+
+    def __init__(self, w3, w1, b3, b1, prec):
+        self.srcs, self.prec = [w3, w1, b3, b1], prec
+        self.cout, self.cin, self.caux = w3.shape[0], w3.shape[1], w1.shape[1]
+        assert w1.shape[0] == self.cout and prec != L.PREC_F32
+        lib = L.load()
+        self.off1 = int(lib.sgd_packed_weight_bytes(self.cout, self.cin, 3, prec))      # the 1x1 units follow the 3x3 ones
+        nbytes = self.off1 + int(lib.sgd_packed_weight_bytes(self.cout, self.caux, 1, prec))
+        dev = w3.device
+        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        self.bias = torch.empty(self.cout, dtype=torch.float32, device=dev)
+        self.amax = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.scale_inv = torch.ones(1, dtype=torch.float32, device=dev)
+        self.cin_p = self.cout_p = 0
+        self.sig = None
+
+    @property
+    def scale_ptr(self):
+        return self.scale_inv.data_ptr()
+
+    def refresh(self, stream):
+        sig = tuple((s.data_ptr(), s._version) for s in self.srcs)
+        if sig == self.sig:
+            return
+        lib = L.load()
+        w3, w1 = (s.detach().contiguous().float() for s in self.srcs[:2])
+        self.amax.zero_()
+        for w in (w3, w1):
+            L.check(lib.sgd_weight_amax(_ptr(w), w.numel(), _ptr(self.amax), stream), "sgd_weight_amax")
+        cin_p, cout_p, cx_p = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        L.check(lib.sgd_pack_weight_scaled(_ptr(w3), _ptr(self.buf), self.cout, self.cin, 3, self.prec, 0, _ptr(self.amax),
+                                           _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p), stream), "sgd_pack_weight_scaled")
+        L.check(lib.sgd_pack_weight_scaled(_ptr(w1), C.c_void_p(self.buf.data_ptr() + self.off1), self.cout, self.caux, 1,
+                                           self.prec, 0, _ptr(self.amax), _ptr(self.scale_inv), C.byref(cx_p), C.byref(cout_p),
+                                           stream), "sgd_pack_weight_scaled")
+        torch.add(self.srcs[2].detach().float(), self.srcs[3].detach().float(), out=self.bias)
+        self.cin_p, self.cout_p = cin_p.value, cout_p.value
+        self._keep = (w3, w1)
         self.sig = sig
 
 
@@ -306,12 +355,13 @@ class _PackBatch:
     def refresh(self, stream):
         if self.members is None or self.table_sig != tuple(p.data_ptr() for _, p, _, _ in self.members):
             self._build()                                          # first use, or a parameter moved (.to(), re-materialised)
-        stale = [(pk, p, cp, op) for pk, p, cp, op in self.members if pk.sig != ((p.data_ptr(), p._version),)]
+        stale = [(pk, p, cp, op) for pk, p, cp, op in self.members
+                 if pk.sig != ((p.data_ptr(), p._version),) and not getattr(pk, "idle", False)]
         if len(stale) >= self.MIN_STALE and os.environ.get("SGDM_BATCHED_PACK", "1") != "0":
             L.check(self.lib.sgd_pack_weights_batched(_ptr(self.jobs), len(self.members), _ptr(self.a_job), _ptr(self.a_first),
                                                       self.n_a, _ptr(self.p_job), _ptr(self.p_first), self.n_p, self.prec,
                                                       stream), "sgd_pack_weights_batched")
-            for pk, p, cp, op in self.members:                     # (fresh members were re-packed too: same bytes)
+            for pk, p, cp, op in self.members:                     # (fresh and idle members were re-packed too: same bytes)
                 pk.cin_p, pk.cout_p = cp, op
                 pk.sig = ((p.data_ptr(), p._version),)
                 if hasattr(pk, "srcs") and pk.scaled and not pk.subpixel:
@@ -325,10 +375,26 @@ class _Program:
         self.ops = []
         self.meta = []
         self.keep = []
+        self.when = []            # per entry: None (always), or the one variant it belongs to: "train" / "infer"
 
-    def add(self, name, fn, *args, flops=0.0, nbytes=0.0):
+    def add(self, name, fn, *args, flops=0.0, nbytes=0.0, when=None):
         self.ops.append((name, fn, args))
         self.meta.append((getattr(fn, "__name__", "op"), flops, nbytes))
+        self.when.append(when)
+
+    def variant(self, train):
+        """the entries of the training (train=True) or the inference forward as a program of their own (same argument
+        objects); the program itself where no entry belongs to one variant only"""
+        if all(w is None for w in self.when):
+            return self
+        p, drop = _Program(), "infer" if train else "train"
+        for op, mt, w in zip(self.ops, self.meta, self.when):
+            if w != drop:
+                p.ops.append(op)
+                p.meta.append(mt)
+                p.when.append(w)
+        p.keep = self.keep
+        return p
 
     def run(self, stream):
         for name, fn, args in self.ops:
@@ -605,7 +671,15 @@ class _Engine:
         # zeroed once, shared by every launch of this engine's programs -- they are ordered on one stream
         self.work_bytes = int(self.lib.sgd_igemm_work_bytes()) if os.environ.get("SGDM_BALANCE", "1") != "0" else 0
         self.work = torch.zeros(max(1, self.work_bytes // 4), dtype=torch.float32, device=dev)
+        self.fused_packs = []     # _FusedPacked of the ResBlocks whose inference forward runs sgd_igemm_fused_aux
+        self.train_packs = []     # the 3x3 / 1x1 packs of those blocks' pair: left stale while the engine serves inference
+        self.train_bufs = []      # (shape, [(igemm args, field)]) of buffers only the training forward writes: allocated by its first use
         self._build()
+        # Where a ResBlock's skip conv rides in its out conv (_res), the forward exists in two variants: the inference program
+        # with the fused launches, the training program with the pair (dropout, and the tape's descriptors).  `prog` is the
+        # variant of the last prepare(); both share every other entry.
+        self._progs = {False: self.prog.variant(False), True: self.prog.variant(True)}
+        self.prog = self._progs[False]
 
     # ---- helpers
     def buf(self, *shape, dtype=torch.float32):
@@ -618,6 +692,16 @@ class _Engine:
         (bf16x3 keeps the exact kernel: 8 mantissa bits per half do not hold the softmax weights).  The single-product
         modes take their x3 sibling's core (f16 -> split, bf16 -> exact): the cores are a small share of the step"""
         return self.lib.sgd_attention_split if self.prec in (L.PREC_F16X3, L.PREC_F16) else self.lib.sgd_attention
+
+    def program(self, train):
+        """the forward program of one variant, its buffers allocated"""
+        if train and self.train_bufs:
+            for shape, refs in self.train_bufs:
+                t = self.buf(*shape)
+                for a, field in refs:
+                    setattr(a, field, t.data_ptr())
+            self.train_bufs = []
+        return self._progs[bool(train)]
 
     def pack(self, names, ksize, pad=None, subpixel=False):
         pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad, subpixel)
@@ -661,9 +745,11 @@ class _Engine:
 
     def igemm(self, tag, x0, c0, y, cout, pk, *, x1=None, c1=0, conv=None, m=0, rows_per_n=0,
               pro=L.PRO_NONE, silu=0, pa=None, pb=None, pc=None, bias=None, res=None, res_mode=L.RS_NONE,
-              y_ld=None, y_off=0, orows=(0, 0, 0), stats=False, launch=True):
+              y_ld=None, y_off=0, orows=(0, 0, 0), stats=False, launch=True, when=None, aux=None, res_later=False):
         """stats=True: the epilogue also writes the GroupNorm statistics of y (consumed by gn() through
-        sgd_stats_reduce instead of a sgd_chan_stats pass over the tensor)"""
+        sgd_stats_reduce instead of a sgd_chan_stats pass over the tensor).  y=None: the output pointer is set later
+        (train_bufs; res_later: so is the residual's).  when: the program variant this launch belongs to (_Program.add).
+        aux=(x0, c0, x1, c1): the launch is sgd_igemm_fused_aux with this second input (pk: a _FusedPacked)."""
         a = L.IgemmArgs()
         a.x0, a.x1, a.c0, a.c1 = x0.data_ptr(), (x1.data_ptr() if x1 is not None else 0), c0, c1
         rows_n = conv[0] if conv is not None else (m // rows_per_n if rows_per_n else 0)
@@ -681,7 +767,7 @@ class _Engine:
         a.bias = bias.data_ptr() if bias is not None else 0
         a.res = res.data_ptr() if res is not None else 0
         a.res_mode = res_mode
-        a.y = y.data_ptr() + 4 * y_off
+        a.y = y.data_ptr() + 4 * y_off if y is not None else 0
         a.cout = cout
         a.y_ld = y_ld if y_ld is not None else cout
         a.orows_in, a.orows_out, a.orow_off = orows
@@ -705,7 +791,9 @@ class _Engine:
         if stats and os.environ.get("SGDM_FUSED_STATS", "1") != "0":
             parts = self.lib.sgd_conv3_narrow_in_parts(conv[3], conv[4]) if narrow else self.lib.sgd_igemm_stats_parts(C.byref(a))
             if parts > 0:
-                sbuf = self.buf(rows_n, parts, 2, cout)
+                prev = self.stats_of.get(y.data_ptr())
+                # (the second producer of y -- the other variant of a fused ResBlock -- writes the slots the first one has)
+                sbuf = prev[0] if prev is not None and prev[1:] == (parts, cout) else self.buf(rows_n, parts, 2, cout)
                 a.stats = sbuf.data_ptr()
                 self.stats_of[y.data_ptr()] = (sbuf, parts, cout)
         self.prog.keep.append((a, pk))
@@ -716,7 +804,15 @@ class _Engine:
         taps = (4 if conv[6] == L.RS_UP2_SUBPIXEL else 9) if conv is not None else 1
         cin = c0 + c1
         flops = 2.0 * rows * cout * taps * cin
-        nbytes = 4.0 * (rows_in * cin + rows * cout * (2 if res is not None else 1) + taps * cin * cout)
+        nbytes = 4.0 * (rows_in * cin + rows * cout * (2 if res is not None or res_later else 1) + taps * cin * cout)
+        if aux is not None:                            # the 1x1 product's work rides in this launch's totals
+            ax0, ac0, ax1, ac1 = aux
+            xa = L.IgemmAux(x0=ax0.data_ptr(), x1=ax1.data_ptr() if ax1 is not None else 0, c0=ac0, c1=ac1)
+            flops += 2.0 * rows * cout * (ac0 + ac1)
+            nbytes += 4.0 * (rows * (ac0 + ac1) + (ac0 + ac1) * cout)
+            self.prog.keep.append(xa)
+            self.prog.add(tag, self.lib.sgd_igemm_fused_aux, C.byref(a), C.byref(xa), flops=flops, nbytes=nbytes, when=when)
+            return a
         if narrow:
             wsrc, fn = pk.srcs[0], self.lib.sgd_conv3_narrow_in
             x_p, b_p, y_p, s_p = _ptr(x0), C.c_void_p(a.bias or 0), C.c_void_p(a.y), C.c_void_p(a.stats or 0)
@@ -744,7 +840,7 @@ class _Engine:
                 return fn(x_p, pa_p, pb_p, int(silu), w_p, b_p, y_p, nimg, ho, wo, c0, cout, y_ld, stream)
             self.prog.add(tag, sgd_conv3_narrow_out, flops=flops, nbytes=nbytes)
         elif launch:        # launch=False: descriptor only (the backward's weight gradient reads it)
-            self.prog.add(tag, self.lib.sgd_igemm, C.byref(a), flops=flops, nbytes=nbytes)
+            self.prog.add(tag, self.lib.sgd_igemm, C.byref(a), flops=flops, nbytes=nbytes, when=when)
         return a
 
     def gn(self, tag, srcs, hw, gname, film=None, film_ld=0, eps=GN_EPS):
@@ -905,20 +1001,33 @@ class _Engine:
             a2, b2 = self.gn(p + ".out_layers.0", [(h1, cout)], ho * wo, p + ".out_layers.0")
         sums2 = self._last_sums
         ask = None
+        conv2 = (n, ho, wo, ho, wo, 1, L.RS_NONE)
+        kw2 = dict(conv=conv2, pro=L.PRO_AFFINE_NC, silu=1, pa=a2, pb=b2, stats=True)
+        fuse = cin != cout and self._fuse_skip_ok(cout, conv2, c0, c1)
+        pair = "train" if fuse else None                 # fused: the pair below is the TRAINING forward's, the inference one fuses
         if cin != cout:
             assert ud is None
-            skip = self.buf(n, hh, ww, cout)
-            ask = self.igemm(p + ".skip_connection", t0, c0, skip, cout,
-                             self.pack([p + ".skip_connection.weight"], 1), x1=t1, c1=c1, m=n * hh * ww,
-                             bias=P(p + ".skip_connection.bias"))
+            skip = None if fuse else self.buf(n, hh, ww, cout)     # (fused: allocated by the first training forward)
+            pks = self.pack([p + ".skip_connection.weight"], 1)
+            ask = self.igemm(p + ".skip_connection", t0, c0, skip, cout, pks, x1=t1, c1=c1, m=n * hh * ww,
+                             bias=P(p + ".skip_connection.bias"), when=pair)
             res, res_mode = skip, L.RS_NONE
         else:
             assert t1 is None
             res, res_mode = t0, rs
         y = self.buf(n, ho, wo, cout)
-        ac2 = self.igemm(p + ".out_layers.3", h1, cout, y, cout, self.pack([p + ".out_layers.3.weight"], 3),
-                         conv=(n, ho, wo, ho, wo, 1, L.RS_NONE), pro=L.PRO_AFFINE_NC, silu=1, pa=a2, pb=b2,
-                         bias=P(p + ".out_layers.3.bias"), res=res, res_mode=res_mode, stats=True)
+        pk2 = self.pack([p + ".out_layers.3.weight"], 3)
+        ac2 = self.igemm(p + ".out_layers.3", h1, cout, y, cout, pk2,
+                         bias=P(p + ".out_layers.3.bias"), res=res, res_mode=res_mode, when=pair, res_later=fuse, **kw2)
+        if fuse:
+            # y = conv3x3(act(h1)) + conv1x1(x) + b3 + bs as ONE GEMM over K = 9 cout + cin (sgd_igemm_fused_aux): no skip tensor
+            # written and read back, eleven launches fewer per evaluation of the flagship model
+            self.train_bufs.append(((n, hh, ww, cout), [(ask, "y"), (ac2, "res")]))
+            fpk = _FusedPacked(P(p + ".out_layers.3.weight"), P(p + ".skip_connection.weight"), P(p + ".out_layers.3.bias"),
+                               P(p + ".skip_connection.bias"), self.prec)
+            self.fused_packs.append(fpk)
+            self.train_packs += [pks, pk2]
+            self.igemm(p + ".out_layers.3", h1, cout, y, cout, fpk, bias=fpk.bias, when="infer", aux=(t0, c0, t1, c1), **kw2)
         pbox, sbox = C.c_float(0.0), C.c_uint32(0)
         self.drops.append((ac2, pbox, sbox))                  # nn.Dropout sits in front of conv2 (openaimodel.py:272)
         self.tape.append(dict(kind="res", drop_p=pbox, drop_seed=sbox, p=p,
@@ -928,11 +1037,31 @@ class _Engine:
                               y=y, ss=ss))
         return (y, cout, ho, wo)
 
+    def _fuse_skip_ok(self, cout, conv, ac0, ac1):
+        """may this ResBlock's inference forward run its skip conv inside its out conv?  The library decides
+        (sgd_igemm_fused_aux_ok: split modes, the lean 3x3 geometry, the 128-column tile, ...); SGDM_FUSE_SKIP=0: never"""
+        if os.environ.get("SGDM_FUSE_SKIP", "1") == "0":
+            return False
+        q = L.IgemmArgs()
+        q.mode, (q.n, q.hi, q.wi, q.ho, q.wo, q.stride, q.resample) = L.MODE_CONV3, conv
+        q.c0, q.cout, q.y_ld, q.prec = cout, cout, cout, self.prec
+        q.pro, q.pro_silu = L.PRO_AFFINE_NC, 1
+        # (tune = 0, no dropout, no residual: what igemm() gives the fused entry.  The launch applies the same rule to the
+        # descriptor it gets, so a forward launch that ever carried tune bits would fail loudly (SGD_ERR_ARG) rather than fall
+        # back to the pair: ask with those bits here then.  grid_cap does not enter the rule.)
+        xa = L.IgemmAux(c0=ac0, c1=ac1)
+        return bool(self.lib.sgd_igemm_fused_aux_ok(C.byref(q), C.byref(xa)))
+
     # ---- execution
-    def refresh(self, stream):
+    def refresh(self, stream, train=False):
+        for pk in self.train_packs:                # inference: neither the pair's packs nor (training) the fused ones are repacked
+            pk.idle = not train
         if getattr(self, "_pack_batch", None) is None or len(self._pack_batch.packs) != len(self.packed):
             self._pack_batch = _PackBatch(self.packed, self.prec, self.dev)
         self._pack_batch.refresh(stream)
+        if not train:
+            for pk in self.fused_packs:
+                pk.refresh(stream)
         for a, pk in self._late:
             a.cin_p, a.cout_p = pk.cin_p, pk.cout_p
         for hook in self.refresh_hooks:
@@ -1023,7 +1152,8 @@ class _Engine:
         m, n = self.m, self.n
         stream = torch.cuda.current_stream().cuda_stream
         self.poll_health()
-        self.refresh(stream)
+        self.prog = self.program(train)
+        self.refresh(stream, train)
         # training step of a data-parallel job: the persistent conv grid leaves CUs to the gradient exchange that runs on a
         # side stream under the backward (ddp.reserved_cus); every other evaluation owns the device
         from .ddp import reserved_cus

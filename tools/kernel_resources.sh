@@ -13,8 +13,8 @@ txt = sys.stdin.read()
 for blk in txt.split("- .agpr_count")[1:]:
     g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
     name = g("name")
-    m = re.search(r"igemm_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)", name)
-    short = ("igemm<BN=%s,PREC=%s,VEC=%s,TAPS=%s,DEFER=%s>" % m.groups()) if m else name[:60]
+    m = re.search(r"igemm_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)", name)
+    short = ("igemm<BN=%s,PREC=%s,VEC=%s,TAPS=%s,DEFER=%s,AUX=%s>" % m.groups()) if m else name[:60]
     print("%-52s vgpr %3s sgpr %3s vspill %3s sspill %3s scratch %5s lds %6s" % (short, g("vgpr_count"), g("sgpr_count"),
           g("vgpr_spill_count"), g("sgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))
 '
