@@ -76,6 +76,27 @@ namespace {
 #define KEEP_LIVE(x) (void)(x)
 #endif
 
+// All N quads in registers at ONE point (an empty asm that reads them): loads issued into them must all be in flight together
+// and are waited for once.  Without it the scheduler, short of registers, issued a batch's residual loads one at a time into one
+// register tuple, each with its own wait -- a serial round trip per quad.
+#define SGD_Q4(q, i) "v"((q)[i]), "v"((q)[(i) + 1]), "v"((q)[(i) + 2]), "v"((q)[(i) + 3])
+template <int N>
+__device__ __forceinline__ void quads_landed(const f32x4 (&q)[N]) {
+    static_assert(N == 1 || N == 2 || N == 4 || N == 8 || N == 16, "quads per batch");
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (N == 1) asm volatile("" :: "v"(q[0]));
+    else if constexpr (N == 2) asm volatile("" :: "v"(q[0]), "v"(q[1]));
+    else if constexpr (N == 4) asm volatile("" :: SGD_Q4(q, 0));
+    else if constexpr (N == 8) asm volatile("" :: SGD_Q4(q, 0), SGD_Q4(q, 4));
+    else asm volatile("" :: SGD_Q4(q, 0), SGD_Q4(q, 4), SGD_Q4(q, 8), SGD_Q4(q, 12));
+#endif
+}
+
+// LDS-typed pointers: a read through one is a ds_read (lgkmcnt); through a generic pointer the compiler emits a flat load,
+// which counts in vmcnt AND lgkmcnt and is waited for with both at zero -- behind every store still in flight
+typedef const __attribute__((address_space(3))) float* lds_float_cptr;
+typedef const __attribute__((address_space(3))) f32x4* lds_f32x4_cptr;
+
 // ---------------------------------------------------------------------------------------------
 // LDS element packing per precision
 // ---------------------------------------------------------------------------------------------
@@ -417,12 +438,14 @@ struct IgemmBlock {
         bias_lds = a.cout_p <= BIAS_LDS_MAX;        // very wide layers (all FiLM projections as one GEMM) read it from global
         // DEFER kernels (3x3, 128-column tiles, 16-byte outputs, no or same-row residual, bias in LDS): the epilogue of every
         // tile but a block's last runs on the LOADER waves.  Measured (round 3, compile-time ablations at UNet batch 80): the
-        // epilogue costs a compute wave 8..10 us per tile -- 30..40 % of a 128-channel 3x3 layer, 12..14 % of a 512-channel
-        // one -- and nearly all of it is waiting: vmcnt counts loads and stores in issue order, so the residual loads cost a
+        // epilogue cost a compute wave 8..10 us per tile -- 30..40 % of a 128-channel 3x3 layer, 12..14 % of a 512-channel
+        // one -- and nearly all of it was waiting: vmcnt counts loads and stores in issue order, so the residual loads cost a
         // round trip per batch and the next tile's first weight wait sits behind the acknowledgement of all 16 stores, with
         // the matrix pipe idle (moving the epilogue into the next K loop of the SAME wave moves the stall, it does not remove
         // it: tried).  So the compute waves copy their accumulators to an LDS staging tile (stg, [BM][BN + 4] floats: 0.3 us)
         // and go on; the loaders, whose own waits have a whole chunk period of slack, drain it slice by slice.
+        // (Most of that round-3 figure was not the counter's doing but the generated code's: every store of a tile waited
+        // with vmcnt(0) for the store before it -- see epilogue().  The drain below never had that pattern: it is branch-free.)
         stg = bias_s + a.cout_p;                         // [BM][STG_LD], DEFER only (sgd_igemm sizes the allocation)
 
         tid = threadIdx.x; lane = tid & 63;
@@ -1411,14 +1434,34 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::epi
         }
         {
             // Column slots cs = (column block nt, quad gq) of the lane's output: c = cb + nt * CBW + gq * 8.
-            // load phase: bias + residual of a batch of slots x row blocks -- independent loads in flight (the compiler
-            // may not hoist them itself: y and res could alias) -- then the stores.  Every batch is one exposed memory
-            // round trip for a wave that has nothing else to issue, so batches are as big as the registers allow: with
-            // the 16x16x32 form (operands not carried across the epilogue) ALL of a tile's 16 residual quads.
+            // A batch of slots x row blocks runs in three phases.  (a) all its loads: bias (LDS), residual, the producers'
+            // slabs of a split tile -- independent loads in flight (the compiler may not hoist them itself: y and res could
+            // alias).  (b) v = acc * wsk + bias (+ residual) of EVERY quad, in unconditional code and pinned: one wait for
+            // the loads of (a), and nothing left for the compiler to sink into the predicated blocks of (c).  (c) the
+            // predicated stores, back to back.  Stores count in vmcnt: with the arithmetic inside each `if (okm)` block
+            // (whose skip edge bypasses the block before it) every store was preceded by a wait for its operands with a
+            // count of zero, that is for the acknowledgement of the store before it -- 8..16 serial round trips per tile.
+            // Every batch is one exposed memory round trip for a wave that has nothing else to issue, so batches are as
+            // big as the registers allow.  With the 16x16x32 form that is 8 residual quads (one column slot, all 8 row
+            // blocks): the loaded quads of a batch are all live at one point (quads_landed) next to the 64 accumulators, and
+            // with all 16 of a tile the instance spilled 125 registers -- while the scheduler, left to itself, fitted 16
+            // by loading the second slot's quads one at a time into one register tuple, a wait behind each.
             constexpr int CS = CBN * QPB;                                      // column slots per lane
-            constexpr int QB = M16 ? ((RES == 2 || PART) ? 1 : (CBN > 2 ? 2 : CBN)) : ((RES == 2 || NT > 1) ? 1 : 2);   // slots per batch
+            constexpr int QB = M16 ? ((RES || PART) ? 1 : (CBN > 2 ? 2 : CBN)) : ((RES == 2 || NT > 1) ? 1 : 2);   // slots per batch
             constexpr int RBB = M16 ? (RES == 2 || RB < 4 ? 2 : ((PART || CBN > 2) ? 4 : RB)) : RB;   // row blocks per batch
             static_assert(RB % RBB == 0 && CS % QB == 0, "batches must tile the wave's rows and columns");
+            // the bias through an LDS-typed pointer: a ds_read, waited for with lgkmcnt alone (as a generic pointer it was a
+            // flat load, which counts in both counters and can only be waited for with vmcnt(0) lgkmcnt(0))
+            const lds_f32x4_cptr bias_q = reinterpret_cast<lds_f32x4_cptr>((lds_float_cptr)bias_s);
+            // EARLY: the three phases.  The scalar-input instances (VEC = false: cold, input channel counts that are no
+            // multiple of 4) keep the parent's form -- loads, then the arithmetic in front of each store, generic bias
+            // pointer: their 3x3 split-mode instance sits at 256 registers with nothing to give and spills to scratch
+            // (which every launch of the kernel then pays for) with the phases apart.  -DSGDM_EPI_EARLY_ALL=1 compiles them
+            // the new way (development: tools/epilogue_waits.py with SGDM_EXTRA_FLAGS shows the spill count)
+#ifndef SGDM_EPI_EARLY_ALL
+#define SGDM_EPI_EARLY_ALL 0
+#endif
+            constexpr bool EARLY = VEC || SGDM_EPI_EARLY_ALL;
 #pragma unroll
             for (int q0 = 0; q0 < CS; q0 += QB) {
             f32x4 s1[QB], s2[QB];
@@ -1429,7 +1472,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::epi
             // (opaque per batch: the addresses of a batch's rows are formed here, not hoisted as RB 64-bit values)
 #pragma unroll
             for (int mt = mb0; mt < mb0 + RBB; ++mt) asm volatile("" : "+v"(orw[mt]), "+v"(rrw[mt]));
-            f32x4 rv[QB][RBB];
+            // ---- (a) loads
+            f32x4 rv[QB][RBB];                        // bias + residual, then the finished output quad
             f32x4 pv[QB][RBB];
             if constexpr (PART) {
 #pragma unroll
@@ -1442,34 +1486,88 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::epi
                         pv[cs - q0][mt - mb0] = sum;
                     }
             }
+            constexpr int NL = (RES == 2 ? 4 : (RES ? 1 : 0)) * (ABL(2) ? 0 : 1);     // residual quads per output quad
+            f32x4 lr[QB * RBB * (NL ? NL : 1)];
+            if constexpr (EARLY && NL > 0) {
 #pragma unroll
-            for (int cs = q0; cs < q0 + QB; ++cs) {
-                const int c = cb + (cs / QPB) * CBW + (cs % QPB) * 8;
-                const int cl = c < a.cout ? c : 0;    // clamped: the quad is skipped below
-                f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-                if (bias_lds) bv = *reinterpret_cast<const f32x4*>(bias_s + cl);
-                else if (a.bias && !ABL(2)) bv = ld4(a.bias + cl);
+                for (int cs = q0; cs < q0 + QB; ++cs) {
+                    const int c = cb + (cs / QPB) * CBW + (cs % QPB) * 8;
+                    const int cl = c < a.cout ? c : 0;    // clamped: the quad is skipped below
 #pragma unroll
-                for (int mt = mb0; mt < mb0 + RBB; ++mt) {
-                    f32x4& r = rv[cs - q0][mt - mb0];
-                    r = bv;
-                    if ((RES == 1 || RES == 3) && !ABL(2)) r += ld4(a.res + (long)rrw[mt] * a.cout + cl);
-                    if (RES == 2 && !ABL(2)) {
-                        const long rw = (long)a.wo * 2 * a.cout;
-                        const float* rp = a.res + (long)rrw[mt] * a.cout;
-                        r += 0.25f * (ld4(rp + cl) + ld4(rp + a.cout + cl) + ld4(rp + rw + cl) + ld4(rp + rw + a.cout + cl));
+                    for (int mt = mb0; mt < mb0 + RBB; ++mt) {
+                        f32x4* l = lr + ((cs - q0) * RBB + (mt - mb0)) * NL;
+                        const float* rp = a.res + (long)rrw[mt] * a.cout + cl;
+                        l[0] = ld4(rp);
+                        if constexpr (RES == 2) {
+                            const long rw = (long)a.wo * 2 * a.cout;
+                            l[1] = ld4(rp + a.cout);
+                            l[2] = ld4(rp + rw);
+                            l[3] = ld4(rp + rw + a.cout);
+                        }
                     }
                 }
             }
+            // the bias AFTER the residual loads are issued: its two sources (LDS / global, for layers wider than BIAS_LDS_MAX)
+            // write the same registers, so the compiler drains vmcnt in front of the LDS read -- behind the batch's loads
+            // that wait is the batch's own; in front of them it was a wait for the acknowledgement of the previous batch's
+            // stores before the first load went out
+            f32x4 bvs[QB];
+#pragma unroll
+            for (int cs = q0; cs < q0 + QB; ++cs) {
+                const int c = cb + (cs / QPB) * CBW + (cs % QPB) * 8;
+                const int cl = c < a.cout ? c : 0;
+                f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+                if (bias_lds) bv = EARLY ? bias_q[cl >> 2] : *reinterpret_cast<const f32x4*>(bias_s + cl);
+                else if (a.bias && !ABL(2)) bv = ld4(a.bias + cl);
+                bvs[cs - q0] = bv;
+            }
+            if constexpr (EARLY && NL > 0) quads_landed(lr);
+#pragma unroll
+            for (int cs = q0; cs < q0 + QB; ++cs) {
+                const int c = cb + (cs / QPB) * CBW + (cs % QPB) * 8;
+                const int cl = c < a.cout ? c : 0;
+                const f32x4 bv = bvs[cs - q0];
+#pragma unroll
+                for (int mt = mb0; mt < mb0 + RBB; ++mt) {
+                    f32x4& r = rv[cs - q0][mt - mb0];
+                    const f32x4* l = lr + ((cs - q0) * RBB + (mt - mb0)) * NL;
+                    r = bv;
+                    if constexpr (EARLY) {
+                        if constexpr (NL == 1) r += l[0];
+                        if constexpr (NL == 4) r += 0.25f * (l[0] + l[1] + l[2] + l[3]);
+                    } else if constexpr (NL > 0) {
+                        const float* rp = a.res + (long)rrw[mt] * a.cout + cl;
+                        const long rw = (long)a.wo * 2 * a.cout;
+                        if constexpr (NL == 1) r += ld4(rp);
+                        else r += 0.25f * (ld4(rp) + ld4(rp + a.cout) + ld4(rp + rw) + ld4(rp + rw + a.cout));
+                    }
+                }
+            }
+            // ---- (b) every output quad of the batch, masked rows and clamped columns included (their addresses are valid
+            // and their values are never stored)
+            auto finish = [&](int cs, int mt) __attribute__((always_inline)) {
+                f32x4 v = accq(acc, mt, cs / QPB, cs % QPB);
+                if constexpr (PART) v += pv[cs - q0][mt - mb0];
+                return v * wsk + rv[cs - q0][mt - mb0];
+            };
+            if constexpr (EARLY) {
+#pragma unroll
+                for (int cs = q0; cs < q0 + QB; ++cs)
+#pragma unroll
+                    for (int mt = mb0; mt < mb0 + RBB; ++mt) {
+                        f32x4& r = rv[cs - q0][mt - mb0];
+                        r = finish(cs, mt);
+                        asm volatile("" : "+v"(r));      // (the quad as ONE 128-bit operand: it stays a register tuple for the store)
+                    }
+            }
+            // ---- (c) stores
 #pragma unroll
             for (int cs = q0; cs < q0 + QB; ++cs) {
                 const int c = cb + (cs / QPB) * CBW + (cs % QPB) * 8;
                 if (c >= a.cout) continue;            // uniform within a lane half / a row of 16 lanes
 #pragma unroll
                 for (int mt = mb0; mt < mb0 + RBB; ++mt) {
-                    f32x4 v = accq(acc, mt, cs / QPB, cs % QPB);
-                    if constexpr (PART) v += pv[cs - q0][mt - mb0];
-                    v = v * wsk + rv[cs - q0][mt - mb0];
+                    const f32x4 v = EARLY ? rv[cs - q0][mt - mb0] : finish(cs, mt);
                     if (okm[mt]) {
                         if (!(DBG(8)) && !ABL(1)) *reinterpret_cast<f32x4*>(a.y + (long)orw[mt] * a.y_ld + c) = v;
                         else KEEP_LIVE(v);
@@ -1519,7 +1617,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::epi
                             const float* pp = reinterpret_cast<const float*>(part_base + (size_t)(((mt * CBN + nt) * QPB + gq) * NCOMP) * 16) + j;
                             for (int pi = 0; pi < nparts; ++pi) x += pp[pi * (SLAB / 4)];
                         }
-                        x = x * wsk + (bias_lds ? bias_s[c] : (a.bias ? a.bias[c] : 0.f));
+                        // (the bias as in the 16-byte path: an LDS read, not a flat load -- but for the scalar-input instances)
+                        x = x * wsk + (bias_lds ? (VEC ? ((lds_float_cptr)bias_s)[c] : bias_s[c]) : (a.bias ? a.bias[c] : 0.f));
                         if (RES == 1 || RES == 3) x += rp[c];
                         if (RES == 2) {
                             const long rw = (long)a.wo * 2 * a.cout;
@@ -1879,7 +1978,8 @@ __device__ __forceinline__ void IgemmBlock<BN, PREC, VEC, TAPS, DEFER, AUX>::com
                 if constexpr (M16) {
                     // the WEIGHTS of the next tile's first step (requested by the last step, 16 registers) are carried: asked
                     // for again here they would sit behind the acknowledgement of the epilogue's 16 stores (vmcnt is in
-                    // order); the input units come from LDS
+                    // order, and the stores -- issued back to back since the epilogue computes a batch's quads before its
+                    // first store -- are all still in flight at this point); the input units come from LDS
 #pragma unroll
                     for (int st = 0; st < RB; ++st) ring[st].load(a0 + aoff[st % RB], lane >> 4);
                 } else {
@@ -1997,9 +2097,12 @@ int launch(const KArgs& ka, int vec, int taps, size_t smem, hipStream_t st) {
 #ifndef SGDM_DEV_AUX
 #define SGDM_DEV_AUX false
 #endif
+#ifndef SGDM_DEV_VEC
+#define SGDM_DEV_VEC true
+#endif
 #define SGD_DISPATCH_BODY(P)                                                                                        \
     const KArgs& ka = *reinterpret_cast<const KArgs*>(kap); (void)bn; (void)vec; (void)taps;                         \
-    return launch1<SGDM_DEV_BN, P, true, SGDM_DEV_ONE, SGDM_DEV_DEFER, SGDM_DEV_AUX>(ka, smem, st);
+    return launch1<SGDM_DEV_BN, P, SGDM_DEV_VEC, SGDM_DEV_ONE, SGDM_DEV_DEFER, SGDM_DEV_AUX>(ka, smem, st);
 #else
 #define SGD_DISPATCH_BODY(P)                                                                                        \
     const KArgs& ka = *reinterpret_cast<const KArgs*>(kap);                                                         \

@@ -5,7 +5,9 @@ sgd_igemm_args (the library reads no environment), anything else is put into the
 ABI 15; rounds are interleaved, median and min reported, outputs of all variants compared with the first.
 
     python tools/ab_conv.py --variants base=lib/libsgdm_hip_base.so new=lib/libsgdm_hip.so new256=lib/libsgdm_hip.so:tune=2 \
-        --shapes 80,256,256,64 80,512,512,32 ... [--rounds 7] [--reps 20] [--prec f32|f16x3|bf16x3|f16|bf16] [--plain]
+        --shapes 80,256,256,64 80,512,512,32 ... [--rounds 7] [--reps 20] [--prec f32|f16x3|bf16x3|f16|bf16] [--plain] [--stats] [--res-mode same|avgpool|up]
+--stats: the launches also write their GroupNorm statistic slots (where the shape has any); every variant's output and slots are
+compared with the first variant's BIT FOR BIT (`bits=same` / `bits=DIFF`, `stats=same` / `stats=DIFF`) next to the relative difference.
 shape = n,cin,cout,hw[,ks[,up]]: up = 1 -- the nearest-x2-upsample conv of a hw x hw input (ResBlock up / Upsample, no
 residual); a variant with `subpixel=1` runs it as the sub-pixel conv (SGD_RS_UP2_SUBPIXEL) on the sub-pixel pack:
     --variants direct=lib/libsgdm_hip.so sub128=lib/libsgdm_hip.so:subpixel=1:tune=1 sub256=lib/libsgdm_hip.so:subpixel=1:tune=2 \
@@ -21,6 +23,10 @@ ap.add_argument("--variants", nargs="+", required=True)
 ap.add_argument("--shapes", nargs="+", required=True)
 ap.add_argument("--rounds", type=int, default=7); ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--prec", default="f16x3"); ap.add_argument("--plain", action="store_true")
+ap.add_argument("--stats", action="store_true")
+ap.add_argument("--res-mode", default="same", choices=["same", "avgpool", "up"],
+                help="3x3 launches: the residual is a map of the output's size, the 2x2 average of one at twice the resolution "
+                     "(ResBlock down) or the nearest pixel of one at half the resolution (ResBlock up)")
 a = ap.parse_args()
 LIBDIR = os.path.dirname(L.LIB_PATH)
 
@@ -49,7 +55,8 @@ for shp in a.shapes:
     g = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(n, hw, hw, cin, device="cuda", generator=g)
     w = torch.randn(cout, cin, ks, ks, device="cuda", generator=g) / (cin * ks * ks) ** 0.5
-    bias = torch.randn(cout, device="cuda", generator=g); res = torch.randn(n, hw, hw, cout, device="cuda", generator=g)
+    rhw = hw if ks != 3 or a.res_mode == "same" else (2 * hw if a.res_mode == "avgpool" else hw // 2)
+    bias = torch.randn(cout, device="cuda", generator=g); res = torch.randn(n, rhw, rhw, cout, device="cuda", generator=g)
     pa, pb = 1 + 0.3 * torch.randn(n, cin, device="cuda", generator=g), 0.3 * torch.randn(n, cin, device="cuda", generator=g)
     runs = []
     for name, lib, env in variants:
@@ -78,6 +85,8 @@ for shp in a.shapes:
         if not a.plain:
             q.pro, q.pro_silu, q.pa, q.pb = L.PRO_AFFINE_NC, 1, pa.data_ptr(), pb.data_ptr()
             q.res = 0 if up else res.data_ptr()
+            if ks == 3 and not up:
+                q.res_mode = {"same": L.RS_NONE, "avgpool": L.RS_AVGPOOL2, "up": L.RS_UP2}[a.res_mode]
         q.w, q.cin_p, q.cout_p, q.bias = buf.data_ptr(), cp.value, op.value, bias.data_ptr()
         q.y, q.cout, q.y_ld, q.prec = y.data_ptr(), cout, cout, prec
         q.tune, q.grid_cap = int(env.get("tune", 0)), int(env.get("grid_cap", 0))
@@ -87,7 +96,13 @@ for shp in a.shapes:
             if name not in WORK:
                 WORK[name] = torch.zeros(wb // 4, device="cuda")
             q.work, q.work_bytes = WORK[name].data_ptr(), wb
-        runs.append((name, lib, env, q, y, (buf, sinv), []))
+        stt = None
+        if a.stats and hasattr(lib, "sgd_igemm_stats_parts"):
+            parts = int(lib.sgd_igemm_stats_parts(C.byref(q)))
+            if parts > 0:
+                stt = torch.full((n, parts, 2, cout), float("nan"), device="cuda")
+                q.stats = stt.data_ptr()
+        runs.append((name, lib, env, q, y, (buf, sinv, stt), []))
 
     def launch(lib, env, q, reps):
         old = {k: os.environ.get(k) for k in env}
@@ -113,5 +128,9 @@ for shp in a.shapes:
     for name, lib, env, q, y, buf, ts in runs:
         med, mn = statistics.median(ts), min(ts)
         diff = float((y - ref).abs().max() / ref.abs().max())
-        line += f"  {name} {med:.4f} ms ({fl / med / 1e9:.0f} TF, min {mn:.4f}, d={diff:.1e})"
+        same = lambda u, v: u.shape == v.shape and bool(torch.equal(u.view(torch.int32), v.view(torch.int32)))
+        bits = "same" if same(y, ref) else "DIFF"
+        if buf[2] is not None and runs[0][5][2] is not None:
+            bits += " stats=" + ("same" if same(buf[2], runs[0][5][2]) else "DIFF")
+        line += f"  {name} {med:.4f} ms ({fl / med / 1e9:.0f} TF, min {mn:.4f}, d={diff:.1e} bits={bits})"
     print(line, flush=True)
