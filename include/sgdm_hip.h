@@ -477,6 +477,26 @@ int sgd_v_step(const float* x, const float* v_out, const float* z /* may be NULL
                int32_t cfg_mode, float w, const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
                const sgd_vstep_row* row_dev, float* x0_hist, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
                void* stream);
+/* Ancestral update of a learned-variance model (hparam learn_sigma, sgdm_amd/diffusion.py; Nichol & Dhariwal 2021; no
+ * counterpart in the reference): ONE launch per UNet evaluation of the 'native' sampler.  `out` is the RAW network output,
+ * [2b, hw, 2c] ([cond ; uncond]) when cfg_mode != 0, else [b, hw, 2c]: channels [0, c) predict the mean and pass through
+ * guided() (the three cfg_mode forms above, each product rounded before it is added), channels [c, 2c) are the variance
+ * interpolation and are read from the CONDITIONAL half alone (GLIDE's rule: guidance acts on the mean only).  Per element:
+ *   x0    = k0 * x - k1 * m                  (eps: sqrt_recip_ac, sqrt_recipm1_ac | x0: 0, -1 | v: sqrt_ac, sqrt_1mac)
+ *   clip != 0: x0 = min(max(x0, -1), 1)
+ *   acc   = k2 * x0 + k3 * x                 (k2, k3: the posterior mean coefficients)
+ *   kz != 0: frac = (v + 1) * 0.5;  lv = frac * max_log + (1 - frac) * min_log;  acc = acc + (exp(0.5 * lv) * kz) * z
+ *   x_out = acc;   x0_out = x0 when x0_out != NULL
+ * kz is the temperature, 0 on the last row; z is NOT read when kz == 0 (it may be NULL then).  The row is read from DEVICE
+ * memory (formed by the caller in double and rounded once) and no by-value argument changes between steps, so one captured
+ * step replays for a whole trajectory.  x, z, x_out, x0_out are NCHW [b, c, hw]; x_out == x allowed; x0_out must not alias x, z
+ * or x_out.  Additive entry (ABI unchanged at 25). */
+typedef struct sgd_lvstep_row {
+    float k0, k1, k2, k3, max_log, min_log, kz, pad;
+} sgd_lvstep_row;
+int sgd_ddpm_lv_step(const float* x, const float* out, const float* z /* may be NULL when kz == 0 */, int32_t cfg_mode, float w,
+                     const sgd_lvstep_row* row_dev, int32_t clip, int32_t b, int32_t c, int32_t hw, float* x_out,
+                     float* x0_out /* or NULL */, void* stream);
 /* Guidance pass (sampling kwargs cfg_interval / cfg_rescale, sgdm_amd/diffusion.py; no counterpart in the reference): the
  * guided network output, formed BEFORE the update instead of inside it, with the weight read from DEVICE memory -- no
  * by-value argument changes between steps, so one captured step serves a whole trajectory and any per-step weight schedule --
@@ -726,6 +746,46 @@ int sgd_loss_fwd(const float* out, const float* x0, const float* noise, const in
 int sgd_loss_bwd(const float* out, const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
                  const float* sqrt_1mac, const float* wt, const float* gper /* DEVICE [b]: dL / d per_w */, float gscale,
                  int32_t par, int32_t kind, int32_t b, int64_t chw, float* gout /* [b, chw] */, void* stream);
+
+/* Hybrid loss of a learned-variance model, L_simple + lambda L_vlb (csrc/lvloss.hip; hparam learn_sigma, sgdm_amd/train.py;
+ * Nichol & Dhariwal 2021; additive entries, no counterpart in the reference).  out is the model output NCHW [b, 2c, hw]:
+ * m = out[:, :c] predicts the trained target, v = out[:, c:] interpolates the log-variance; x0, noise NCHW [b, c, hw]; t DEVICE
+ * int64 [b]; `tables` is a HOST struct of DEVICE fp32 [T] tables (sqrt_recip_ac / sqrt_recipm1_ac may be NULL unless par 0).
+ * Per element, every product rounded before it is added (par, kind, target and l as sgd_loss_fwd):
+ *   l     = l(m - target)                                   the bits of sgd_loss_fwd's term on the mean half
+ *   x_t   = sqrt_ac x0 + sqrt_1mac noise                    (the bits of sgd_q_sample)
+ *   x0p   = sqrt_recip_ac x_t - sqrt_recipm1_ac m (par 0) | m (par 1) | sqrt_ac x_t - sqrt_1mac m (par 2), not clipped
+ *   mu_th = mean_coef1 x0p + mean_coef2 x_t;   mu_q = mean_coef1 x0 + mean_coef2 x_t
+ *   frac  = (v + 1) * 0.5;   lv = frac max_log + (1 - frac) min_log;   lq = min_log
+ *   t > 0 : L = 0.5 (-1 + lv - lq + exp(lq - lv) + (mu_q - mu_th)^2 exp(-lv)) / ln 2                       (fp32)
+ *   t == 0: inv = exp(-0.5 lv), d = x0 - mu_th, Phi(u) = 0.5 (1 + tanh(sqrt(2/pi) (u + 0.044715 u^3))),
+ *           cp = Phi(inv (d + 1/255)), cm = Phi(inv (d - 1/255)), P = cp (x0 < -0.999) | 1 - cm (x0 > 0.999) | cp - cm,
+ *           L = -log max(P, 1e-12) / ln 2                   (in double from the fp32 inputs, forward and backward)
+ * sgd_lv_loss_fwd: per_raw[n] = mean l, per_w[n] = wt[t[n]] per_raw[n] (wt NULL: weight 1), per_vlb[n] = mean L in bits/dim,
+ *   means over c*hw; one workgroup per sample, sums as sgd_loss_fwd (double partials, fixed fold order, no atomics).
+ * sgd_lv_loss_bwd: gout [b, 2c, hw] = d (sum_n gper_w[n] per_w[n] + gper_vlb[n] per_vlb[n]) / d out with the gradient of L
+ *   STOPPED at the mean (the paper's rule): the mean half is sgd_loss_bwd's gradient (gscale 1) bit for bit, the variance half
+ *   gper_vlb[n] / (c hw) * dL/dlv * 0.5 (max_log - min_log), dL/dlv = 0.5 (1 - exp(lq - lv) - (mu_q - mu_th)^2 exp(-lv)) / ln 2
+ *   for t > 0 and the analytic derivative of the decoder term for t == 0 (0 where P < 1e-12: torch's clamp rule).  gper_w and
+ *   gper_vlb are read from DEVICE memory: no by-value argument depends on the step.
+ * 16-byte accesses when hw % 4 == 0 and every tensor is 16-byte aligned, one float per lane otherwise.  SGD_ERR_ARG, nothing
+ * launched: b, c or hw <= 0, par / kind out of range, a NULL pointer the call needs. */
+typedef struct sgd_lv_tables {
+    const float* sqrt_ac;
+    const float* sqrt_1mac;
+    const float* sqrt_recip_ac;
+    const float* sqrt_recipm1_ac;
+    const float* mean_coef1;
+    const float* mean_coef2;
+    const float* max_log;
+    const float* min_log;
+} sgd_lv_tables;
+int sgd_lv_loss_fwd(const float* out, const float* x0, const float* noise, const int64_t* t, const sgd_lv_tables* tables,
+                    const float* wt /* [T] or NULL = 1 */, int32_t par, int32_t kind, int32_t b, int32_t c, int32_t hw,
+                    float* per_raw /* [b] */, float* per_w /* [b] */, float* per_vlb /* [b] */, void* stream);
+int sgd_lv_loss_bwd(const float* out, const float* x0, const float* noise, const int64_t* t, const sgd_lv_tables* tables,
+                    const float* wt, const float* gper_w /* DEVICE [b] */, const float* gper_vlb /* DEVICE [b] */, int32_t par,
+                    int32_t kind, int32_t b, int32_t c, int32_t hw, float* gout /* [b, 2c, hw] */, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Optimizer step: AdamW (lightning_module_common.py:20-42: torch.optim.AdamW defaults, decoupled weight decay)

@@ -41,6 +41,10 @@ FILE_FLAGS["guide.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["vstep.hip"] = ["-ffp-contract=off"]
 # loss.hip: the same -- the weighted loss's target and gradient (sgd_loss_fwd / sgd_loss_bwd), product by product
 FILE_FLAGS["loss.hip"] = ["-ffp-contract=off"]
+# lvloss.hip, lvstep.hip: the same -- the hybrid loss of a learned-variance model (sgd_lv_loss_fwd / sgd_lv_loss_bwd: the
+# simple term carries sgd_loss_fwd's bits) and its ancestral update (sgd_ddpm_lv_step), product by product
+FILE_FLAGS["lvloss.hip"] = ["-ffp-contract=off"]
+FILE_FLAGS["lvstep.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

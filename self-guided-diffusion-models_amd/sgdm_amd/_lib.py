@@ -71,6 +71,12 @@ class PackJob(C.Structure):
                 ("transpose", i32), ("own_amax", i32), ("reserved0", i32)]
 
 
+class LvTables(C.Structure):
+    """mirror of ``struct sgd_lv_tables`` (include/sgdm_hip.h): device addresses of the [T] tables of sgd_lv_loss_*"""
+    _fields_ = [(k, vp) for k in ("sqrt_ac", "sqrt_1mac", "sqrt_recip_ac", "sqrt_recipm1_ac", "mean_coef1", "mean_coef2",
+                                  "max_log", "min_log")]
+
+
 # name -> (restype, argtypes); every symbol include/sgdm_hip.h declares
 SIGNATURES = {
     "sgd_abi_version": (i32, []),
@@ -165,6 +171,9 @@ SIGNATURES = {
     "sgd_v_step": (i32, [vp, vp, vp, i32, f32, vp, vp, vp, dvp, vp, i32, i32, i32, i32, vp, vp]),
     "sgd_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
     "sgd_loss_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, dvp, f32, i32, i32, i32, i64, vp, vp]),
+    "sgd_lv_loss_fwd": (i32, [vp, vp, vp, vp, C.POINTER(LvTables), vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "sgd_lv_loss_bwd": (i32, [vp, vp, vp, vp, C.POINTER(LvTables), vp, dvp, dvp, i32, i32, i32, i32, i32, vp, vp]),
+    "sgd_ddpm_lv_step": (i32, [vp, vp, vp, i32, f32, dvp, i32, i32, i32, i32, vp, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

@@ -23,6 +23,11 @@ Also without a counterpart, on the training side: the hparam ``loss_weighting`` 
 Salimans & Ho 2022; 'p2', Choi et al. 2022; 'table'): ``loss_weight_table`` builds the per-timestep weights on the loss of the
 trained target, ``Schedule_DDPM`` keeps them as the buffer ``loss_weights`` and ``train.p_losses_hip`` applies them inside the
 loss kernels (include/sgdm_hip.h: sgd_loss_fwd / sgd_loss_bwd).
+Also without a counterpart, learned variance (Nichol & Dhariwal 2021): the hparams ``learn_sigma`` / ``vlb_weight`` (the UNet is
+2C channels wide; buffers ``lv_max_log`` / ``lv_min_log``; ``train.p_losses_hip`` adds the variational bound through
+sgd_lv_loss_fwd / sgd_lv_loss_bwd), the 'native' update ``_LVUpdate`` (sgd_ddpm_lv_step) that samples with it, the sampling kwarg
+``native_steps`` = K (``native_times``, ``native_rows``: a strided ancestral chain, fixed or learned variance), the C-row head of
+every other sampler (``_StepRunner.head``) and ``LatentDiffusion.calc_bpd``.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -263,6 +268,91 @@ def v_form_option(sk, method, ac_visited=None, par=None):
     return form
 
 
+def native_steps_option(sk, method, T):
+    """None | K: the sampling kwarg ``native_steps`` of the 'native' sampler, a strided ancestral chain over K of the T
+    training times (2 <= K <= T).  ValueError, before anything is loaded or launched, on another sampler or out of range.
+    Pure host code."""
+    K = (sk or {}).get("native_steps")
+    if K is None:
+        return None
+    if method != "native":
+        raise ValueError(f"native_steps strides the 'native' sampler; '{method}' takes num_timesteps")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 2 <= K <= T:
+        raise ValueError(f"native_steps={K!r}: an int, 2 .. {T}")
+    return int(K)
+
+
+def native_times(K, T):
+    """the K visited training times s_i = round(i (T - 1) / (K - 1)), ascending: improved-DDPM's ``space_timesteps`` with one
+    section.  Always contains 0 and T - 1"""
+    return np.asarray([int(round(i * (T - 1) / (K - 1))) for i in range(K)], dtype=np.int64)
+
+
+NATIVE_KINDS = ("ddpm", "v_native", "lv_native")
+
+
+def native_rows(ac, kind, parameterization, temperature):
+    """rows of one of the three native update kinds -- 'ddpm' [K, 5] (sgd_ddpm_step), 'v_native' [K, 8] (sgd_vstep_row),
+    'lv_native' [K, 8] (sgd_lvstep_row) -- for an ancestral chain over the ``alphas_cumprod`` subsequence ``ac`` (ascending
+    times, row 0 the last step).  Everything in float64 from ``ac`` and rounded once: the chain's own
+    beta'_i = 1 - ac_i / ac_{i-1} (ac_{-1} = 1), its posterior mean coefficients, beta~' and, for learned variance, log beta'
+    and log beta~' with entry 0 taken from entry 1 (the released improved-DDPM convention).  ``temperature``: one factor per
+    row; row 0 has no noise.  Also returns the float64 beta'."""
+    if kind not in NATIVE_KINDS:
+        raise ValueError(f"native update kind {kind!r}: one of {NATIVE_KINDS}")
+    ac = np.asarray(ac, dtype=np.float64)
+    K = ac.shape[0]
+    temp = np.asarray([float(v) for v in temperature], dtype=np.float64)
+    assert temp.shape[0] == K, (temp.shape, K)
+    ap = np.concatenate([[1.0], ac[:-1]])
+    beta = 1.0 - ac / ap
+    c1 = beta * np.sqrt(ap) / (1.0 - ac)
+    c2 = (1.0 - ap) * np.sqrt(1.0 - beta) / (1.0 - ac)
+    pv = beta * (1.0 - ap) / (1.0 - ac)
+    zero = np.zeros(K)
+    with np.errstate(divide="ignore"):
+        if parameterization == "x0":
+            k0, k1 = zero, -np.ones(K)              # x0 = 0 * x - (-1) * out, exact
+        elif parameterization == "v" and kind == "lv_native":
+            k0, k1 = np.sqrt(ac), np.sqrt(1.0 - ac)     # the learned-variance update reads the raw output as v
+        elif parameterization in ("eps", "v"):
+            # 'ddpm' rows of a 'v' model too: on the eps form the step runner has changed v to eps (sgd_v_to_eps) before
+            # sgd_ddpm_step reads it, as ``step_table`` assumes ('v_native' rows carry neither scalar)
+            k0, k1 = np.sqrt(1.0 / ac), np.sqrt(1.0 / ac - 1.0)
+        else:
+            raise NotImplementedError(f"parameterization '{parameterization}'")
+        kz = temp.copy()
+        kz[0] = 0.0
+        if kind == "lv_native":
+            mx, mn = np.log(beta), np.log(pv)
+            mn[0] = mn[1]
+            tab = np.stack([k0, k1, c1, c2, mx, mn, kz, zero], 1)
+        else:
+            kz = kz * np.exp(0.5 * np.log(np.maximum(pv, 1e-20)))
+            kz[0] = 0.0
+            tab = np.stack([k0, k1, c1, c2, kz], 1) if kind == "ddpm" else np.stack([c2, c1, zero, kz, zero, zero, zero, zero], 1)
+    return torch.tensor(tab, dtype=torch.float64).float(), beta
+
+
+LV_NATIVE_REFUSED = ("dtp", "noise_dropout", "cfg_interval", "cfg_rescale", "v_form")
+
+
+def lv_native_option(sk):
+    """the 'native' sampler of a learned-variance model (update kind 'lv_native', sgd_ddpm_lv_step) refuses what its one
+    launch does not implement -- dynamic thresholding, noise dropout, the guidance schedule, the data form of 'v' (its row
+    already avoids dividing by sqrt(alphas_cumprod) for 'v') -- with ValueError, before anything is loaded or launched"""
+    sk = sk or {}
+    if sk.get("dtp", 1) < 1.0:
+        raise ValueError("learn_sigma 'native': dynamic thresholding (dtp < 1) is not implemented")
+    if sk.get("noise_dropout", 0) > 0:
+        raise ValueError("learn_sigma 'native': noise_dropout is not implemented")
+    if sk.get("cfg_interval") is not None or sk.get("cfg_rescale", 0) != 0:
+        raise ValueError("learn_sigma 'native': cfg_interval / cfg_rescale are not implemented")
+    if sk.get("v_form", "eps") == "data":
+        raise ValueError("learn_sigma 'native': v_form='data' is not needed, the row of a 'v' model never divides by "
+                         "sqrt(alphas_cumprod)")
+
+
 def cfg_schedule(times, cond_scale, scale_mode, interval=None):
     """per UNet EVALUATION of a trajectory (``times``: its time argument, one entry per evaluation -- PNDM's list repeats
     times): (guided, weight).  An evaluation is guided when ``t_lo <= t <= t_hi`` (``interval`` None: always) and then has
@@ -291,9 +381,34 @@ class _StepRunner:
         self.scheduled = self.rescale > 0 or self.interval is not None
         # 'data' (sampling kwarg v_form, checked by the sampler: v_form_option): no v -> eps pass, the update reads v itself
         self.form = "data" if (sk or {}).get("parameterization", "eps") == "v" and (sk or {}).get("v_form") == "data" else "eps"
+        # a learned-variance model's output is 2C wide.  ``lv`` (kwarg lv_native, set by the 'native' sampler of such a
+        # model): the update reads the RAW output, both halves, whatever the parameterization; every other update ignores the
+        # variance half and must not pay for it: the engine's head conv runs over weight rows [0, C) (``head``).  Which of
+        # the two it is follows from the model's width, not from a kwarg a direct caller could forget.
+        self.lv = bool((sk or {}).get("lv_native", False))
         self.lib = L.load()
         self._drop = {}
-        self.v = _v_tables(sk, dev)
+        self.v = None if self.lv else _v_tables(sk, dev)
+
+    def width(self, out_c, Cc):
+        """what a step does with a network output of ``out_c`` channels for an image of ``Cc``: 'raw' (the learned-variance
+        update reads all 2C), 'narrow' (2C wide, the update reads the mean half only) or 'plain'.  ValueError for any other
+        width: the step kernels would read the output with the wrong stride"""
+        if self.lv:
+            if out_c != 2 * Cc:
+                raise ValueError(f"the learned-variance 'native' update needs a network output of {2 * Cc} channels, not {out_c}")
+            return "raw"
+        if out_c == Cc:
+            return "plain"
+        if out_c == 2 * Cc:
+            return "narrow"
+        raise ValueError(f"the network output has {out_c} channels, the image {Cc}: {Cc}, or {2 * Cc} for a learned-variance "
+                         "model, is what the samplers read")
+
+    def head(self, Cc):
+        """the ``head`` argument of the drop-in model's engines (UNetModelBase._engine) for an image of ``Cc`` channels: the
+        mean rows alone when the model is 2C wide and the update ignores the variance half"""
+        return Cc if self.model is not None and self.width(self.model.out_channels, Cc) == "narrow" else None
 
     def fused_cfg(self):
         """whether a step takes the batch-doubled evaluation whose guided score is formed inside the step kernel: the
@@ -340,12 +455,12 @@ class _StepRunner:
             if self.scheduled and not guided:
                 # the conditional prediction alone: one evaluation at B, RNG consumed as forward(cond_drop_prob=p0) does
                 mask = m._draw_mask(B, 0.0, x.device) if self.cond_only_mask() else None
-                eng, mode, w = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B), 0, 0.0
+                eng, mode, w = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B, self.head(Cc)), 0, 0.0
                 out = eng.eps_nhwc
             else:
                 has_mask, p = self.drop_mask(B, x.device)
                 mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B)
+                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc))
                 out, mode, w = eng.eps_nhwc, m._scale_mode(), float(kw["cond_scale"])
                 if self.scheduled:
                     g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
@@ -355,6 +470,11 @@ class _StepRunner:
             e = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
             return self.v_to_eps(x, out, t, mode, w, B, Cc, e, _stream()), 0, 0.0, B, Cc
         e = self.fn(x, t, **self.kwargs).contiguous()       # generic path: guided output, NCHW
+        width = self.width(e.shape[1], Cc)
+        if width == "raw":                                  # [B, 2C, H, W] re-laid as the raw output [B, hw, 2C]; not hot
+            return e.float().reshape(B, 2 * Cc, -1).permute(0, 2, 1).contiguous(), 0, 0.0, B, Cc
+        if width == "narrow":
+            e = e[:, :Cc].contiguous()                      # the variance half is ignored
         if self.form == "data":
             return e.float(), 0, 0.0, B * Cc, 1
         if self.v is not None:
@@ -404,6 +524,7 @@ class _Update:
     NOISE = False
     EXTRAS = False
     x0 = None                   # clipped x0 prediction of the last launch (snapshot steps clone it), where there is one
+    native_steps = None         # 'native' only: the sampling kwarg of a strided chain (part of a captured step's cache key)
 
     def __init__(self, kind, sk, clip, temperature=1.0):
         self.lib, self.kind, self.clip, self.temperature = L.load(), kind, clip, float(temperature)
@@ -517,6 +638,25 @@ class _VUpdate(_Update):
                                     row_dev, _ptr(self.x0), self.clip, b, c, hw, _ptr(x_out), st), "sgd_v_step")
 
 
+class _LVUpdate(_Update):
+    """``sgd_ddpm_lv_step`` (kind 'lv_native'): the ancestral update of a learned-variance model.  ``eps`` is the RAW network
+    output, 2C channels wide ([2B | B, hw, 2C]): the kernel guides the mean channels and reads the variance channels from
+    the conditional half.  A row is one ``sgd_lvstep_row`` (include/sgdm_hip.h); the parameterization lives in its (k0, k1),
+    the per-step temperature in its kz.  Neither noise dropout nor dynamic thresholding (``lv_native_option`` refuses them)."""
+
+    COEF = (8, torch.float32)
+    NOISE = True
+
+    def alloc(self, img):
+        self.z, self.x0 = torch.empty_like(img), torch.empty_like(img)
+
+    draw = _DDUpdate.draw
+
+    def launch(self, st, x, out, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True):
+        L.check(self.lib.sgd_ddpm_lv_step(_ptr(x), _ptr(out), _ptr(self.z if z is None else z), mode, w, row_dev, self.clip,
+                                          b, c, hw, _ptr(x_out), _ptr(self.x0 if want_x0 else None), st), "sgd_ddpm_lv_step")
+
+
 class _GraphedStep:
     """One CFG sampling step -- UNet at 2B (~135 launches) + the fused update -- captured into a hipGraph
     (``torch.cuda.CUDAGraph`` capture of the stream the C-ABI launchers are given), cached on the model per
@@ -546,7 +686,8 @@ class _GraphedStep:
         cond, layout = kw.get("cond"), kw.get("layout")
         sig = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         prec = L.PREC_BY_NAME[m.hip_precision]
-        eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec)
+        # (a learned-variance model under an update that ignores the variance half: the engine with the C-row head)
+        eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]))
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
         # (the data form of 'v' captures another update launch and no conversion: a third kind of entry)
         par = "eps" if runner.v is None else ("v", runner.v[0].numel()) + (("data",) if runner.form == "data" else ())
@@ -554,7 +695,7 @@ class _GraphedStep:
         # of graphs, when an interval is requested, is one entry)
         w = None if runner.scheduled else float(kw["cond_scale"])
         key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, m._scale_mode(), sig(cond), sig(layout), par,
-               (runner.rescale, runner.interval is not None))
+               (runner.rescale, runner.interval is not None), (runner.lv, runner.head(img.shape[1]), upd.native_steps))
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
         if g is None:                                       # the key covers all of ``upd`` that the capture baked in
@@ -604,6 +745,8 @@ class _GraphedStep:
         self.replays = dict(guided=0, cond=0)
 
         def tail(st, eps, mode, w):
+            if runner.lv:                               # the raw 2C-wide output, guided inside the update
+                return upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
             if data:
                 return upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img, t=self.t, tables=self.v)
             if self.v is not None:                      # v -> guided eps at this step's time; the update reads it with mode 0
@@ -622,7 +765,7 @@ class _GraphedStep:
         if runner.interval is not None:
             # the conditional prediction alone: the engine at B over the same img / t / cond / layout; its mask stays all-false
             # (``u1`` is only drawn into, to consume the RNG like the model's own single evaluation)
-            eng1 = self.eng1 = m._engine(B, img.shape[2], img.shape[3], eng.prec)
+            eng1 = self.eng1 = m._engine(B, img.shape[2], img.shape[3], eng.prec, runner.head(Cc))
             self.u1 = torch.zeros(B, device=dev) if runner.cond_only_mask() else None
             self.mask1 = torch.zeros(B, dtype=torch.bool, device=dev) if runner.cond_only_mask() else None
             eng1.prepare(img, self.t, self.cond, self.layout, self.mask1)
@@ -796,6 +939,23 @@ class Schedule_DDPM(nn.Module):
                              "carries no information; use 'v' (or 'x0')")
         # optional hparams (not in the reference): per-timestep loss weights, buffer ``loss_weights`` (sgdm_amd/train.py)
         self.loss_weighting = loss_weighting_option(h)
+        # optional hparams (not in the reference; Nichol & Dhariwal 2021): the network is 2C channels wide and the second half
+        # of its output interpolates the reverse-process log-variance between the buffers lv_min_log and lv_max_log; the loss
+        # is L_simple + vlb_weight * L_vlb (sgdm_amd/train.py).  The UNet's width is checked where it is attached
+        # (LatentDiffusion.set_denoise_fn) and on every output (p_losses).
+        self.learn_sigma = bool(getattr(h, "learn_sigma", False))
+        self.vlb_weight = None
+        if self.learn_sigma:
+            if h.v_posterior != 0:
+                raise ValueError(f"learn_sigma with v_posterior={h.v_posterior!r}: the learned variance interpolates between "
+                                 "beta and beta~, v_posterior must be 0")
+            vw = getattr(h, "vlb_weight", None)
+            self.vlb_weight = h.num_timesteps / 1000.0 if vw is None else float(vw)
+            if not (self.vlb_weight >= 0 and np.isfinite(self.vlb_weight)):
+                raise ValueError(f"vlb_weight={vw!r} must be a finite number >= 0")
+            oc, ic = getattr(h, "out_channels", None), getattr(h, "channels", None)
+            if oc is not None and ic is not None and oc != 2 * ic:
+                raise ValueError(f"learn_sigma needs out_channels == 2 * channels, not {oc} and {ic}")
         self.register_schedule(given_betas=h.given_betas, beta_schedule=h.beta_schedule, timesteps=h.num_timesteps,
                                linear_start=h.linear_start, linear_end=h.linear_end, cosine_s=h.cosine_s)
 
@@ -851,6 +1011,16 @@ class Schedule_DDPM(nn.Module):
             lw = (torch.tensor(table, dtype=torch.float64).float() if scheme == "table" else
                   loss_weight_table(self.alphas_cumprod, h.parameterization, scheme, gamma, k))
             reg("loss_weights", lw.to(dev), persistent=False)
+        if self.learn_sigma:
+            # float64 from the fp32 buffers, rounded once.  lv_min_log[0] is entry 1 (the released improved-DDPM convention),
+            # not the 1e-20 clip of posterior_log_variance_clipped, whose -46 would make the t = 0 range 37 nats wide
+            b64, a64 = self.betas.detach().cpu().double().numpy(), self.alphas_cumprod.detach().cpu().double().numpy()
+            ap64 = np.append(1.0, a64[:-1])
+            with np.errstate(divide="ignore"):
+                mn = np.log(b64 * (1.0 - ap64) / (1.0 - a64))
+            mn[0] = mn[1]
+            reg("lv_max_log", to_torch(np.log(b64)), persistent=False)
+            reg("lv_min_log", to_torch(mn), persistent=False)
         reg("snr_derivative", torch.zeros(1000, dtype=torch.float32).to(dev))
         reg("SNR", torch.zeros(1000, dtype=torch.float32).to(dev))
         # host copies of the per-step scalars of the fused step kernel (fp32 math as on the device)
@@ -921,24 +1091,43 @@ class Schedule_DDPM(nn.Module):
             # a direct call: this object is the training schedule, so its own hparam and buffers stand in for the kwargs
             sk = dict(sk, parameterization="v", sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
                       sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
-        order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps
-        # the 'x0' rows (0, -1) never read the infinite entries of a zero-terminal-SNR table: nothing to refuse there
-        visited = None if h.parameterization == "x0" else self.alphas_cumprod.detach().cpu().numpy()[
-            list(range(timesteps)) if order is None else [int(i) for i in order]]
+        order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps (rows of the chain)
+        # sampling kwarg native_steps = K (not in the reference): a strided chain over K of the table's times
+        K = native_steps_option(sk, "native", timesteps)
+        times = np.arange(timesteps, dtype=np.int64) if K is None else native_times(K, timesteps)
+        lv = self.learn_sigma
+        if lv:
+            lv_native_option(sk)
+            sk = dict(sk, lv_native=True)                # the step runner hands the update the raw 2C-wide output
+        # the 'x0' rows (0, -1) never read the infinite entries of a zero-terminal-SNR table, and the 'v' rows of the
+        # learned-variance update never divide by sqrt(alphas_cumprod): nothing to refuse there
+        visited = None if h.parameterization == "x0" or (lv and h.parameterization == "v") else \
+            self.alphas_cumprod.detach().cpu().numpy()[times[list(range(len(times))) if order is None else [int(i) for i in order]]]
         form = v_form_option(sk, "native", visited)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         if type(temperature) == float or isinstance(temperature, int):
             temperature = [float(temperature)] * timesteps
-        snaps = _Snapshots(timesteps, sk)
+        total = len(times)
+        snaps = _Snapshots(total, sk)
         runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
         clip = 1 if sk["clip_denoised"] else 0
-        if form == "data":
-            upd, tab = _VUpdate("v_native", sk, clip, noise=True), self.vstep_table(temperature)
+        kind = "lv_native" if lv else "v_native" if form == "data" else "ddpm"
+        tab = None
+        if K is not None or lv:
+            # the chain's own coefficients, float64 from the fp32 alphas_cumprod of the visited times (per-step temperatures:
+            # those of the visited times)
+            tab, _ = native_rows(self.alphas_cumprod.detach().cpu().double().numpy()[times], kind, h.parameterization,
+                                 [temperature[int(s)] for s in times])
+        if lv:
+            upd = _LVUpdate(kind, sk, clip)
+        elif form == "data":
+            upd, tab = _VUpdate(kind, sk, clip, noise=True), (self.vstep_table(temperature) if tab is None else tab)
         else:
-            upd, tab = _DDUpdate("ddpm", sk, clip), self.step_table(temperature)
-        stepper = _sampler_step(runner, sk, img, upd, range(timesteps), tab)
-        for i in (reversed(range(0, timesteps)) if order is None else order):
+            upd, tab = _DDUpdate(kind, sk, clip), (self.step_table(temperature) if tab is None else tab)
+        upd.native_steps = K
+        stepper = _sampler_step(runner, sk, img, upd, times, tab)
+        for i in (reversed(range(0, total)) if order is None else order):
             want = i in snaps.rows
             stepper.step(i, None if noise_fn is None else noise_fn(i).to(dev), want)
             if want:
@@ -988,6 +1177,7 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, **kwargs):
+        native_steps_option(sampling_kwargs, self.sampler_type, self.ddpm_num_timesteps)
         self.make_schedule(sampling_kwargs=sampling_kwargs)
         # step_indices (teacher-forced tests) visits only those table rows
         rows = kwargs.get("step_indices") if self.sampler_type == "ddim" else None
@@ -1187,6 +1377,7 @@ class PNDM_Sampler(object):
     def sample(self, shape, sampling_kwargs, log_num_per_prog=100, denoise_sample_fn=None, denoise_sample_fn_kwargs=None,
                **kwargs):
         sk = sampling_kwargs
+        native_steps_option(sk, "pndm", self.ddpm_num_timesteps)
         v_form_option(sk, "pndm")                   # (its own schedule: no zero alphas_cumprod of the model's to visit)
         n = sk["num_timesteps"]
         times, tab = self.plan(n)
@@ -1293,6 +1484,7 @@ class DPMSolverSampler(object):
         sk = sampling_kwargs
         if sk.get("dtp", 1) < 1.0:
             raise ValueError("dpmsolver: dynamic thresholding (dtp < 1) is not implemented for this sampler")
+        native_steps_option(sk, "dpmsolver", self.ddpm_num_timesteps)
         form = v_form_option(sk, "dpmsolver")
         ts, tab = self.plan(sk, form)
         v_form_option(sk, "dpmsolver", sk["alphas_cumprod"].detach().float().cpu().numpy()[ts])
@@ -1342,6 +1534,10 @@ class LatentDiffusion(nn.Module):
         }
 
     def set_denoise_fn(self, denoise_fn, denoise_sample_fn):
+        unet = getattr(denoise_fn, "__self__", denoise_fn)
+        if self.sampler.learn_sigma and isinstance(unet, UNetModelBase) and unet.out_channels != 2 * unet.in_channels:
+            raise ValueError(f"learn_sigma needs a UNet with out_channels == 2 * in_channels (mean and variance halves), not "
+                             f"{unet.out_channels} and {unet.in_channels}")
         self.denoise_fn = denoise_fn
 
         def _denoise_sample_fn(*args, **kwargs):
@@ -1362,6 +1558,33 @@ class LatentDiffusion(nn.Module):
         return p_losses_hip(self, x_start, t, noise, *args, **kwargs)
 
     @torch.no_grad()
+    def calc_bpd(self, x_start, noise_fn=None, **cond_kwargs):
+        """bits/dim of ``x_start`` under a learned-variance model (improved-DDPM's ``calc_bpd_loop``): for t = T-1 .. 0 over
+        the whole batch one q_sample, one UNet evaluation (conditional branch, no dropout: ``denoise_fn(x_t, t,
+        **cond_kwargs)``) and the variational-bound term of the hybrid loss, forward only.  Returns ``vb`` [B, T] (bits/dim per
+        timestep), ``prior_bpd`` [B] = mean KL(N(sa_{T-1} x0, 1 - ac_{T-1}) || N(0, I)) / ln 2 and ``total_bpd`` =
+        vb.sum(1) + prior_bpd.  ``noise_fn(t)``: the q_sample noise of timestep t (tests); default torch.randn_like."""
+        s = self.sampler
+        if not s.learn_sigma:
+            raise ValueError("calc_bpd needs a learned-variance model (hparam learn_sigma): a fixed-variance model has no "
+                             "variational bound to report")
+        from .train import lv_terms
+        T, B = self.hparams.num_timesteps, x_start.shape[0]
+        x_start = x_start.float()
+        vb = torch.empty(B, T, dtype=torch.float32, device=x_start.device)
+        for ti in reversed(range(T)):
+            t = torch.full((B,), ti, dtype=torch.long, device=x_start.device)
+            noise = torch.randn_like(x_start) if noise_fn is None else noise_fn(ti).to(x_start.device)
+            vb[:, ti] = lv_terms(self, x_start, t, noise, cond_kwargs)[2]
+        ac = s.alphas_cumprod[T - 1].double()
+        # KL(N(m, v) || N(0, 1)) = 0.5 (-1 - log v + v + m^2) per element, v = 1 - ac
+        m2 = (ac * x_start.double() ** 2).reshape(B, -1)
+        var = 1.0 - ac
+        prior = (0.5 * (-1.0 - torch.log(var) + var + m2)).mean(1) / np.log(2.0)
+        prior = prior.float()
+        return dict(total_bpd=vb.sum(1) + prior, prior_bpd=prior, vb=vb)
+
+    @torch.no_grad()
     def p_sample_loop(self, sampling_method, shape, sampling_kwargs, **kwargs):
         sk = copy.deepcopy({k: v for k, v in sampling_kwargs.items()})
         sk.update(dict(alphas_cumprod=self.sampler.alphas_cumprod,
@@ -1372,8 +1595,11 @@ class LatentDiffusion(nn.Module):
                            sqrt_one_minus_alphas_cumprod=self.sampler.sqrt_one_minus_alphas_cumprod))
             # a zero-terminal-SNR schedule is sampled on the data form wherever there is one (plms / pndm stay on eps: plms
             # works as long as its spacing does not visit the last timestep, and is refused by the sampler when it does)
-            if self.sampler.zero_terminal_snr and sampling_method in V_FORM_SAMPLERS:
+            # (the 'native' update of a learned-variance model has one form, whose 'v' row never divides by sa)
+            if self.sampler.zero_terminal_snr and sampling_method in V_FORM_SAMPLERS and not (
+                    self.sampler.learn_sigma and sampling_method == "native"):
                 sk.setdefault("v_form", "data")
+        native_steps_option(sk, sampling_method, self.hparams.num_timesteps)     # refused on every other sampler
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(
             shape=shape, denoise_sample_fn=self.denoise_sample_fn, sampling_kwargs=sk, **kwargs)

@@ -15,7 +15,9 @@ walking the forward tape in reverse:
   * attention backward = ``sgd_attention_bwd`` with the forward's log-sum-exp (no score matrix stored);
   * q_sample / MSE loss = ``sgd_q_sample`` / ``sgd_mse_loss``;
   * with the hparam ``loss_weighting`` (not in the reference): the per-timestep weighted loss and its gradient =
-    ``sgd_loss_fwd`` / ``sgd_loss_bwd`` (``_WeightedLossFn``), the target formed on the fly.
+    ``sgd_loss_fwd`` / ``sgd_loss_bwd`` (``_WeightedLossFn``), the target formed on the fly;
+  * with the hparam ``learn_sigma`` (not in the reference): the hybrid loss L_simple + vlb_weight * L_vlb of a 2C-wide model
+    output and its gradient = ``sgd_lv_loss_fwd`` / ``sgd_lv_loss_bwd`` (``_LVLossFn``).
 
 ``loss.backward()`` works because the UNet evaluation is a ``torch.autograd.Function`` whose inputs are the
 trainable parameters; it returns one gradient tensor per parameter in the reference layout.
@@ -1053,6 +1055,167 @@ class _WeightedLossFn(torch.autograd.Function):
         return (gout,) + (None,) * 8
 
 
+# ---- learned variance (hparam learn_sigma; Nichol & Dhariwal 2021): L_simple + vlb_weight * L_vlb.  The torch chain below is
+# the CPU branch of p_losses and the restatement the device kernels (csrc/lvloss.hip) are tested against; it runs in the
+# dtype of its inputs (float64 for gradcheck), except the decoder term, which is always evaluated in double.
+_LN2 = math.log(2.0)
+_SQRT_2_PI = math.sqrt(2.0 / math.pi)
+
+
+def lv_coefs(s, t, shape, par):
+    """the per-sample schedule scalars of the bound, gathered at ``t`` and shaped to broadcast over ``shape``"""
+    names = dict(sa="sqrt_alphas_cumprod", s1="sqrt_one_minus_alphas_cumprod", c1="posterior_mean_coef1",
+                 c2="posterior_mean_coef2", mx="lv_max_log", mn="lv_min_log")
+    if par == "eps":                    # (infinite on a zero-terminal-SNR table, which 'eps' is refused on)
+        names.update(r0="sqrt_recip_alphas_cumprod", r1="sqrt_recipm1_alphas_cumprod")
+    return {k: s._ext(getattr(s, v), t, shape) for k, v in names.items()}
+
+
+def lv_means(par, m, x0, noise, c):
+    """(mu_th, mu_q): the posterior means from the model's x0 prediction (not clipped) and from x0 itself"""
+    xt = c["sa"] * x0 + c["s1"] * noise
+    if par == "eps":
+        x0p = c["r0"] * xt - c["r1"] * m
+    elif par == "x0":
+        x0p = m
+    else:
+        x0p = c["sa"] * xt - c["s1"] * m
+    return c["c1"] * x0p + c["c2"] * xt, c["c1"] * x0 + c["c2"] * xt
+
+
+def lv_logvar(v, mx, mn):
+    frac = (v + 1.0) * 0.5
+    return frac * mx + (1.0 - frac) * mn
+
+
+def lv_kl_bits(mu_th, mu_q, lv, lq):
+    """t > 0: KL(q(x_{t-1} | x_t, x0) || p_theta(x_{t-1} | x_t)) per element, in bits"""
+    dm = mu_q - mu_th
+    e1, e2 = torch.exp(lq - lv), (dm * dm) * torch.exp(-lv)
+    return (0.5 * ((((-1.0 + lv) - lq) + e1) + e2)) / _LN2
+
+
+def lv_decoder_bits(x0, mu_th, lv):
+    """t == 0: the discretized-Gaussian decoder NLL of improved-DDPM per element, in bits; evaluated in double (cp - cm
+    cancels in fp32 from about four standard deviations out) and returned in the dtype of ``lv``"""
+    x, mu, l = x0.double(), mu_th.double(), lv.double()
+    inv, d = torch.exp(-0.5 * l), x - mu
+
+    def phi(u):
+        return 0.5 * (1.0 + torch.tanh(_SQRT_2_PI * (u + 0.044715 * u * u * u)))
+
+    cp, cm = phi(inv * (d + 1.0 / 255.0)), phi(inv * (d - 1.0 / 255.0))
+    p = torch.where(x < -0.999, cp, torch.where(x > 0.999, 1.0 - cm, cp - cm))
+    return (-torch.log(p.clamp(min=1e-12)) / _LN2).to(lv.dtype)
+
+
+def lv_vlb_torch(s, out, x0, noise, t, par):
+    """per_vlb [B]: the mean over C*hw of the bound's term at t, bits/dim; the gradient stops at the mean half"""
+    Cc = x0.shape[1]
+    m, v = out[:, :Cc].detach(), out[:, Cc:]
+    c = lv_coefs(s, t, x0.shape, par)
+    mu_th, mu_q = lv_means(par, m, x0, noise, c)
+    lv = lv_logvar(v, c["mx"], c["mn"])
+    kl = lv_kl_bits(mu_th, mu_q, lv, c["mn"])
+    dec = lv_decoder_bits(x0.expand_as(mu_th), mu_th, lv)
+    first = (t == 0).reshape(-1, *((1,) * (x0.dim() - 1)))
+    return torch.where(first, dec, kl).reshape(len(x0), -1).mean(1)
+
+
+def _lv_tables(s):
+    """the host struct of device tables sgd_lv_loss_* take (include/sgdm_hip.h: sgd_lv_tables), from the schedule's buffers"""
+    return L.LvTables(sqrt_ac=s.sqrt_alphas_cumprod.data_ptr(), sqrt_1mac=s.sqrt_one_minus_alphas_cumprod.data_ptr(),
+                      sqrt_recip_ac=s.sqrt_recip_alphas_cumprod.data_ptr(), sqrt_recipm1_ac=s.sqrt_recipm1_alphas_cumprod.data_ptr(),
+                      mean_coef1=s.posterior_mean_coef1.data_ptr(), mean_coef2=s.posterior_mean_coef2.data_ptr(),
+                      max_log=s.lv_max_log.data_ptr(), min_log=s.lv_min_log.data_ptr())
+
+
+class _LVLossFn(torch.autograd.Function):
+    """(per_w, per_raw, per_vlb) of a learned-variance model's output [B, 2C, H, W] in one launch (sgd_lv_loss_fwd); the
+    gradient for the output -- sgd_loss_bwd's on the mean half, the bound's on the variance half -- in one more
+    (sgd_lv_loss_bwd), which is never entered under no_grad."""
+
+    @staticmethod
+    def forward(ctx, out, x0, noise, t, sched, wt, par, kind):
+        lib = L.load()
+        out = out.contiguous().float()
+        B, Cc, hw = x0.shape[0], x0.shape[1], x0[0, 0].numel()
+        per_raw, per_w, per_vlb = (torch.empty(B, dtype=torch.float32, device=out.device) for _ in range(3))
+        tabs = _lv_tables(sched)
+        L.check(lib.sgd_lv_loss_fwd(_ptr(out), _ptr(x0), _ptr(noise), _ptr(t), C.byref(tabs), _ptr(wt), par, kind, B, Cc, hw,
+                                    _ptr(per_raw), _ptr(per_w), _ptr(per_vlb), torch.cuda.current_stream().cuda_stream),
+                "sgd_lv_loss_fwd")
+        ctx.save_for_backward(out, x0, noise, t, wt)
+        ctx.sched, ctx.par, ctx.kind = sched, par, kind
+        ctx.mark_non_differentiable(per_raw)
+        return per_w, per_raw, per_vlb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper_w, _graw, gper_vlb):
+        out, x0, noise, t, wt = ctx.saved_tensors
+        gper_w, gper_vlb = gper_w.contiguous().float(), gper_vlb.contiguous().float()
+        gout = torch.empty_like(out)
+        tabs = _lv_tables(ctx.sched)
+        L.check(L.load().sgd_lv_loss_bwd(_ptr(out), _ptr(x0), _ptr(noise), _ptr(t), C.byref(tabs), _ptr(wt), gper_w.data_ptr(),
+                                         gper_vlb.data_ptr(), ctx.par, ctx.kind, x0.shape[0], x0.shape[1], x0[0, 0].numel(),
+                                         _ptr(gout), torch.cuda.current_stream().cuda_stream), "sgd_lv_loss_bwd")
+        return (gout,) + (None,) * 7
+
+
+def _simple_torch(loss_type, target, model_output):
+    """the per-sample simple loss as a torch chain (ddpm.py:67-103)"""
+    if loss_type == "l2":
+        return ((target - model_output) ** 2).reshape(len(target), -1).mean(1)
+    if loss_type == "l1":
+        return (target - model_output).abs().reshape(len(target), -1).mean(1)
+    if loss_type == "huber":
+        return torch.nn.functional.smooth_l1_loss(target, model_output, reduction="none").reshape(len(target), -1).mean(1)
+    raise NotImplementedError(f"unknown loss type '{loss_type}'")
+
+
+def lv_loss(s, h, out, x0, noise, t, weights):
+    """(per_w, per_raw, per_vlb) of a learned-variance model's output: the fused kernels on the device, the torch chain
+    elsewhere"""
+    Cc = x0.shape[1]
+    if out.dim() != x0.dim() or out.shape[1] != 2 * Cc:
+        raise ValueError(f"learn_sigma: the model output has {out.shape[1]} channels, the image {Cc}: a UNet with "
+                         f"out_channels == {2 * Cc} is needed")
+    if h.loss_type not in _LOSS_KIND:
+        raise NotImplementedError(f"unknown loss type '{h.loss_type}'")
+    if x0.device.type == "cuda":
+        return _LVLossFn.apply(out, x0, noise, t, s, weights, _LOSS_PAR[h.parameterization], _LOSS_KIND[h.loss_type])
+    par = h.parameterization
+    if par == "x0":
+        target = x0
+    elif par == "eps":
+        target = noise
+    else:
+        target = s._ext(s.sqrt_alphas_cumprod, t, x0.shape) * noise - s._ext(s.sqrt_one_minus_alphas_cumprod, t, x0.shape) * x0
+    raw = _simple_torch(h.loss_type, target, out[:, :Cc])
+    per_w = raw if weights is None else raw * weights[t]
+    return per_w, raw.detach(), lv_vlb_torch(s, out, x0, noise, t, par)
+
+
+@torch.no_grad()
+def lv_terms(diff, x_start, t, noise, cond_kwargs):
+    """(per_w, per_raw, per_vlb) at ``t`` without gradients: q_sample, one evaluation of ``denoise_fn``, the loss's forward
+    (LatentDiffusion.calc_bpd)"""
+    s, h = diff.sampler, diff.hparams
+    x0, nz, tt = x_start.contiguous().float(), noise.contiguous().float(), t.contiguous().to(torch.int64)
+    if x0.device.type == "cuda":
+        x_noisy = torch.empty_like(x0)
+        L.check(L.load().sgd_q_sample(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
+                                      _ptr(s.sqrt_one_minus_alphas_cumprod), x0.shape[0], x0[0].numel(), _ptr(x_noisy),
+                                      torch.cuda.current_stream().cuda_stream), "sgd_q_sample")
+    else:
+        x_noisy = s.q_sample(original_sample=x0, t=tt, noise=nz)
+    out = diff.denoise_fn(x_noisy, tt, **cond_kwargs)
+    out = out[0] if isinstance(out, (tuple, list)) else out
+    weights = s.loss_weights if getattr(s, "loss_weighting", None) is not None else None
+    return lv_loss(s, h, out, x0, nz, tt, weights)
+
+
 def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     """LatentDiffusion.p_losses (ddpm.py:54-86)"""
     fn = getattr(diff.denoise_fn, "__self__", diff.denoise_fn)        # the UNet (a bound forward or the module itself)
@@ -1071,11 +1234,14 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     fused = weights is not None and x_start.device.type == "cuda"
     if fused and h.loss_type not in _LOSS_KIND:
         raise NotImplementedError(f"unknown loss type '{h.loss_type}'")
+    # hparam learn_sigma: the output is 2C wide and the loss is L_simple + vlb_weight * L_vlb (lv_loss); its kernels form
+    # the target themselves, like the weighted ones
+    lv = getattr(s, "learn_sigma", False)
     if x_start.device.type == "cuda":
         x_noisy = torch.empty_like(x_start)
         B = x_start.shape[0]
         x0, nz, tt = x_start.contiguous().float(), noise.contiguous().float(), t.contiguous().to(torch.int64)
-        if h.parameterization == "v" and not fused:   # x_noisy and the target from one read of x_start and noise
+        if h.parameterization == "v" and not fused and not lv:   # x_noisy and the target from one read of x_start and noise
             v_target = torch.empty_like(x_start)
             L.check(lib.sgd_q_sample_v(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
                                        _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy), _ptr(v_target),
@@ -1099,7 +1265,13 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     else:
         target = v_target
     raw = None                          # the unweighted per-sample loss when weighting is on
-    if fused:
+    vlb = None                          # learn_sigma: the per-sample variational-bound term, bits/dim
+    if lv:
+        on_dev = x_start.device.type == "cuda"
+        loss, raw_lv, vlb = lv_loss(s, h, model_output, x0 if on_dev else x_start, nz if on_dev else noise,
+                                    tt if on_dev else t, weights)
+        raw = raw_lv if weights is not None else None
+    elif fused:
         loss, raw = _WeightedLossFn.apply(model_output, x0, nz, tt, s.sqrt_alphas_cumprod, s.sqrt_one_minus_alphas_cumprod,
                                           weights, _LOSS_PAR[h.parameterization], _LOSS_KIND[h.loss_type])
     elif h.loss_type == "l2":
@@ -1115,10 +1287,14 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     if prefix == "train":               # (the UNWEIGHTED per-sample loss: logged per-timestep curves stay comparable)
         loss_dict[f"{prefix}/epoch_stats_y"] = loss.detach() if raw is None else raw
         loss_dict[f"{prefix}/epoch_stats_x"] = t.detach()
+    per = loss
     loss = loss.mean()
     loss_dict[f"{prefix}/ddpm_loss"] = loss.detach()
     if raw is not None:
         loss_dict[f"{prefix}/ddpm_loss_raw"] = raw.mean()
+    if vlb is not None:                 # ddpm_loss stays the simple term; the bound is logged in bits/dim
+        loss_dict[f"{prefix}/vlb"] = vlb.detach().mean()
+        loss = (per + s.vlb_weight * vlb).mean()
     loss = loss + loss_inside
     loss_dict[f"{prefix}/loss"] = loss.detach()
     return loss, loss_dict

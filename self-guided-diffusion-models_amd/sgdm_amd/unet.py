@@ -569,13 +569,18 @@ class UNetModelBase(nn.Module):
         pass
 
     # -------------------------------------------------------------- engine
-    def _engine(self, n, h, w, prec):
+    def _engine(self, n, h, w, prec, head=None):
+        """``head``: inference engines of a learned-variance model (out_channels = 2C) whose sampler ignores the variance half
+        run the head conv over weight rows [0, head) only -- ``eps_nhwc`` is then [n, H, W, head].  An engine of its own:
+        the choice is part of the key (None, the default and the only training engine: every row)"""
         dev = self._device()
         sig = tuple(p.data_ptr() for p in self._all_tensors())
-        key = (n, h, w, prec)
+        if head is not None and not 0 < head < self.out_channels:
+            raise ValueError(f"head={head!r}: a proper prefix of the {self.out_channels} output channels")
+        key = (n, h, w, prec) if head is None else (n, h, w, prec, head)
         eng = self._engines.get(key)
         if eng is None or eng.sig != sig:
-            eng = _Engine(self, n, h, w, prec, dev)
+            eng = _Engine(self, n, h, w, prec, dev, head)
             eng.sig = sig
             self._engines[key] = eng
         return eng
@@ -599,17 +604,18 @@ class UNetModelBase(nn.Module):
         """prob_mask_like (openaimodel.py:462-463): same RNG consumption as the reference"""
         return torch.zeros((n,), device=device).float().uniform_(0, 1) < cond_drop_prob
 
-    def _run(self, x, t, cond, layout, mask, n):
+    def _run(self, x, t, cond, layout, mask, n, head=None):
         """one UNet evaluation at UNet batch n (inputs have n_src = len(x) rows, n % n_src == 0).
-        Returns the engine (eps in eng.eps_nhwc [n, H, W, out_channels])."""
+        Returns the engine (eps in eng.eps_nhwc [n, H, W, out_channels]; ``head``: _engine, inference only)."""
         self._check_runnable(x)
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
+            assert head is None
             from .train import forward_train      # autograd-capable path
             return forward_train(self, x, t, cond, layout, mask, n)
         B, cx, H, W = x.shape
         assert cx == self.in_channels
         prec = L.PREC_BY_NAME[self.hip_precision]
-        eng = self._engine(n, H, W, prec)
+        eng = self._engine(n, H, W, prec, head)
         eng.run(x, t, cond, layout, mask)
         return eng
 
@@ -654,8 +660,9 @@ def grad_health(dev):
 class _Engine:
     """static launch program + workspace for one (UNet batch, H, W, precision)"""
 
-    def __init__(self, model, n, h, w, prec, dev):
+    def __init__(self, model, n, h, w, prec, dev, head=None):
         self.m, self.n, self.h, self.w, self.prec, self.dev = model, n, h, w, prec, dev
+        self.head = head          # UNetModelBase._engine: the head conv's rows [0, head) only (None: all of them)
         self.lib = L.load()
         self.prog = _Program()
         self.packed = []
@@ -931,10 +938,18 @@ class _Engine:
             cur = self._block(f"output_blocks.{i}", blk, [cur, hs.pop()])
         t, c, hh, ww = cur
         a, b = self.gn("out.0", [(t, c)], hh * ww, "out.0")
-        self.eps_nhwc = self.buf(n, hh, ww, m.out_channels)
-        ah = self.igemm("out.2", t, c, self.eps_nhwc, m.out_channels, self.pack(["out.2.weight"], 3),
+        if self.head is None:
+            oc, hpk, hbias = m.out_channels, self.pack(["out.2.weight"], 3), P("out.2.bias")
+        else:
+            # rows [0, head) of the head conv: contiguous views of the two parameters (same storage and version counter, so
+            # the pack follows the parameter like any other)
+            oc, hbias = self.head, P("out.2.bias").detach()[:self.head]
+            hpk = _Packed([P("out.2.weight").detach()[:oc]], 3, self.prec, None, False)
+            self.packed.append(hpk)
+        self.eps_nhwc = self.buf(n, hh, ww, oc)
+        ah = self.igemm("out.2", t, c, self.eps_nhwc, oc, hpk,
                         conv=(n, hh, ww, hh, ww, 1, L.RS_NONE), pro=L.PRO_AFFINE_NC, silu=1, pa=a, pb=b,
-                        bias=P("out.2.bias"))
+                        bias=hbias)
         self.tape.append(dict(kind="head", x=t, c=c, hw=(hh, ww), a=a, b=b, sums=self._last_sums, conv=ah))
 
     def _block(self, prefix, blk, srcs):
