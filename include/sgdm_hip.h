@@ -305,7 +305,10 @@ int sgd_ln_apply(const float* x, const float* gamma, const float* beta, const fl
  *  multi-query attention over [context | null | self] keys (crossattetion_lr.py:90-139)
  * q rows: [b, tq, *] with row stride q_ld, head h at +h*q_hs; k/v rows: [b, tk, *] with row
  * stride kv_ld, head h at +h*kv_hs (0 for multi-query).  out[b, tq, heads*d] head-major.
- * softmax(scale * q.k) ; d in {16, 32, 64, 128}.
+ * softmax(scale * q.k) ; d in {16, 32, 64, 128}.  Any tq, tk >= 1; row strides may exceed the minimum (padding columns are
+ * neither read nor written).  q, k, v are read 16 bytes at a time: the pointers must be 16-byte aligned and q_ld, q_hs, kv_ld,
+ * kv_hs multiples of 4 floats -- anything else, like any other d, is SGD_ERR_ARG (the backward entry points below ask the
+ * same of o, dout, dq, dk, dv and of o_ld, dout_ld).
  * sgd_attention: exact fp32 MFMA.  sgd_attention_split: the same contract in split precision (every fp32 operand as
  * hi + lo f16, three products, fp32 accumulate -- the arithmetic of SGD_PREC_F16X3); out must be 16-byte aligned.
  * -------------------------------------------------------------------------------------- */
@@ -339,12 +342,12 @@ int sgd_cond_select(const void* cond, int32_t is_i64, const uint8_t* mask, const
 int sgd_pack_input(const float* x, const float* layout, const uint8_t* mask, const float* null_layout,
                    int32_t n_src, int32_t n, int32_t cx, int32_t cl, int32_t h, int32_t w,
                    float* out, void* stream);
-/* NHWC [n,h,w,c] -> NCHW [n,c,h,w] */
-/* The same with the layout in its compact on-disk form, expanded on the device exactly as the reference's data
+/* sgd_pack_input with the layout in its compact on-disk form, expanded on the device exactly as the reference's data
  * workers expand it on the CPU (dataset/transforms/complex_ds_common_util.py):
- *   layout_fmt 1: uint8 label map [n_src,h,w] -> one-hot over cl channels, label 255 -> class 0 (stego_to_onehotmask :118-123)
+ *   layout_fmt 1: uint8 label map [n_src,h,w] -> one-hot over cl channels, label 255 -> class 0 (stego_to_onehotmask :118-123);
+ *                 cl <= 255; a label in [cl, 254] has no channel: that pixel's cl layout channels are all 0
  *   layout_fmt 2: int32 boxes [n_src,4] = (x0,y0,x1,y1) in the h x w frame -> mask[y0:y1, x0:x1] = 1, cl == 1
- *                 (get_lostbboxmask :151-162) */
+ *                 (get_lostbboxmask :151-162); x is the column (0 .. w), y the row (0 .. h); x0 >= x1 or y0 >= y1: all 0 */
 int sgd_pack_input_compact(const float* x, const void* layout, int32_t layout_fmt, const uint8_t* mask,
                            const float* null_layout, int32_t n_src, int32_t n, int32_t cx, int32_t cl, int32_t h,
                            int32_t w, float* out, void* stream);
@@ -364,6 +367,7 @@ int sgd_linear_gather(const int64_t* ids, const uint8_t* mask, const float* w, c
 int sgd_linear_sparse_rows(const int64_t* cond, const uint8_t* mask, const float* w, const float* bias, const float* nullproj,
                            int32_t n_src, int32_t n, int32_t nout, int32_t k, float* out, int32_t ldo, void* stream);
 
+/* NHWC [n,h,w,c] -> NCHW [n,c,h,w] */
 int sgd_nhwc_to_nchw(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, float* out, void* stream);
 /* broadcast null_kv rows into the shared K/V buffer (crossattetion_lr.py:95-97):
  * kv[b, row, 0:d] = null_kv[0], kv[b, row, d:2d] = null_kv[1] */
@@ -513,7 +517,6 @@ int sgd_ddpm_lv_step(const float* x, const float* out, const float* z /* may be 
  * between a captured and an eager launch.  guided_out must not alias out.  Additive entry (ABI unchanged at 25). */
 int sgd_cfg_guide(const float* out /* [2b, hw, c] */, int32_t cfg_mode /* 1 | 2 */, const float* w_dev /* DEVICE float[1] */,
                   float rescale, int32_t b, int32_t c, int32_t hw, float* guided_out /* [b, hw, c] */, void* stream);
-/* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100) */
 /* Dynamic thresholding (sampling kwarg dtp < 1; clip_x0_minus_one_to_one, diffusion_utils/util.py:70-79):
  *   s[n] = max(1, quantile(|x0[n]|, dtp)),  x0 <- clamp(x0, -s, s) / s
  * sgd_x0_quantile forms x0 like the step kernels from the same DEVICE row (kind 0: DDPM, kind 1: DDIM) and selects the two
@@ -531,6 +534,7 @@ int sgd_token_pool(const float* cond, int32_t n, int32_t tokens, int32_t c, int3
  * in [rows, 2*inner] = Linear(x) -> out[r, c] = in[r, c] * gelu(in[r, inner + c]), exact erf GELU; inner % 4 == 0 */
 int sgd_geglu(const float* in, int64_t rows, int32_t inner, float* out, void* stream);
 
+/* ((x+1)*127.5).clamp(0,255).to(uint8)  (diffusion_utils/util.py:99-100): fp32 add, fp32 product, truncation */
 int sgd_to_uint8(const float* x, int64_t count, uint8_t* out, void* stream);
 /* guided eps only (forward_with_cond_scale return value): eps_nhwc [2b,h,w,c] -> NCHW [b,c,h,w] */
 int sgd_cfg_combine(const float* eps_nhwc, int32_t cfg_mode, float w, int32_t b, int32_t c, int32_t hw,

@@ -410,13 +410,16 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restr
     const int head = i / tq, qi = i % tq;
     const float* op = o + ((long)b * tq + qi) * o_ld + head * D;
     const float* gp = dout + ((long)b * tq + qi) * dout_ld + head * D;
-    float s = 0.f;
+    // summed in double and rounded once: dS = P (dP - D) cancels where a row's softmax is saturated (dP - D = P2 (dP1 - dP2) for
+    // two keys), so every rounding of D counts 1 / P2 times in dq and dk; the products of two floats are exact in double
+    double s = 0.0;
 #pragma unroll
     for (int d4 = 0; d4 < D / 4; ++d4) {
         f32x4 a = *reinterpret_cast<const f32x4*>(op + d4 * 4), g = *reinterpret_cast<const f32x4*>(gp + d4 * 4);
-        s += a[0] * g[0] + a[1] * g[1] + a[2] * g[2] + a[3] * g[3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s += (double)a[j] * (double)g[j];
     }
-    dvec[((long)b * heads + head) * tq + qi] = s;
+    dvec[((long)b * heads + head) * tq + qi] = (float)s;
 }
 
 // MASKED (sgd_attention_masked_bwd): kmask [batch, tk] bytes, 1 = attend -- a masked key had weight exactly 0 in the forward
@@ -520,9 +523,14 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
         for (int st = 0; st < TT / 32; ++st) {
             if (t0 + st * 32 >= str_n) break;
             // scores / dP tiles: rows = streamed rows (registers), cols = owned rows (lanes)
+            // the dP accumulator starts at -D: dP - D comes out of the MFMA chain itself, its partial sums shrinking towards the
+            // (for a saturated row: small) difference, instead of two independently rounded sums being subtracted afterwards
             f32x16 sacc, pacc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; pacc[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) {
+                sacc[r] = 0.f;
+                pacc[r] = SWEEP == 0 ? -Ds[st * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] : -own_d;
+            }
 #pragma unroll
             for (int s = 0; s < D / 8; ++s) {
                 const f32x4 uf = *reinterpret_cast<const f32x4*>(Us + (st * 32 + li) * LD + s * 8 + lh * 4);
@@ -539,7 +547,6 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
                 const int srow = st * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;      // streamed row of this register
                 const bool ok = (t0 + srow < str_n) && (oi < own_n);
                 const float l = SWEEP == 0 ? Ls[srow] : own_lse;
-                const float dd = SWEEP == 0 ? Ds[srow] : own_d;
                 float p;
                 if (MASKED) {
                     // a masked key is absent from the row's log-sum-exp, so its exponent has no bound: clamp it (valid keys
@@ -551,7 +558,7 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(
                     p = ok ? __expf(sacc[r] * scale - l) : 0.f;
                 }
                 sacc[r] = p;
-                pacc[r] = p * (pacc[r] - dd);
+                pacc[r] = p * pacc[r];                   // pacc holds dP - D
             }
             // gradient accumulation: contract the streamed rows
 #pragma unroll
@@ -1025,6 +1032,13 @@ __global__ __launch_bounds__(256) void linear_attention_bwd_kernel(const float* 
 }
 
 
+// every tensor the backward kernels touch with 16-byte accesses (dvec and lse are read and written one float at a time)
+inline bool attn_bwd_misaligned(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* dq,
+                                const void* dk, const void* dv) {
+    return ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout) | ((uintptr_t)dq) |
+             ((uintptr_t)dk) | ((uintptr_t)dv)) & 15) != 0;
+}
+
 }  // namespace
 
 extern "C" int sgd_attention(const float* q, int32_t q_ld, int32_t q_hs, const float* k, const float* v,
@@ -1075,6 +1089,7 @@ extern "C" int sgd_attention_bwd(const float* q, int32_t q_ld, int32_t q_hs, con
         tk <= 0)
         return SGD_ERR_ARG;
     if ((q_ld & 3) || (q_hs & 3) || (kv_ld & 3) || (kv_hs & 3) || (o_ld & 3) || (dout_ld & 3)) return SGD_ERR_ARG;
+    if (attn_bwd_misaligned(q, k, v, o, dout, dq, dk, dv)) return SGD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int mq = (kv_hs == 0 && heads > 1) ? 1 : 0;
     dim3 gp((heads * tq + 255) / 256, batch), gkv((tk + 127) / 128, mq ? 1 : heads, batch), gq((tq + 127) / 128, heads, batch);
@@ -1106,6 +1121,7 @@ extern "C" int sgd_attention_bwd_split(const float* q, int32_t q_ld, int32_t q_h
         tk <= 0)
         return SGD_ERR_ARG;
     if ((q_ld & 3) || (q_hs & 3) || (kv_ld & 3) || (kv_hs & 3) || (o_ld & 3) || (dout_ld & 3)) return SGD_ERR_ARG;
+    if (attn_bwd_misaligned(q, k, v, o, dout, dq, dk, dv)) return SGD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int mq = (kv_hs == 0 && heads > 1) ? 1 : 0;
     dim3 gp((heads * tq + 255) / 256, batch), gkv((tk + 127) / 128, mq ? 1 : heads, batch), gq((tq + 127) / 128, heads, batch);
@@ -1176,6 +1192,7 @@ extern "C" int sgd_attention_masked_bwd(const float* q, int32_t q_ld, int32_t q_
         tk <= 0)
         return SGD_ERR_ARG;
     if ((q_ld & 3) || (q_hs & 3) || (kv_ld & 3) || (kv_hs & 3) || (o_ld & 3) || (dout_ld & 3)) return SGD_ERR_ARG;
+    if (attn_bwd_misaligned(q, k, v, o, dout, dq, dk, dv)) return SGD_ERR_ARG;
     if (kv_hs == 0 && heads > 1) return SGD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     dim3 gp((heads * tq + 255) / 256, batch), gkv((tk + 127) / 128, heads, batch), gq((tq + 127) / 128, heads, batch);

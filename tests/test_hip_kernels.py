@@ -672,9 +672,10 @@ def test_groupnorm_coefficients_from_partial_statistics(n, c0, parts0, c1, parts
     assert max_rel(sums, s2) < 1e-6 and max_rel(a, a2) < 1e-6 and max_rel(b, b2) < 1e-6
 
 
-@pytest.mark.parametrize("m,n,k,ksplit", [(7, 100, 1234, 5), (160, 256, 5000, 39), (256, 64, 33, 1)])
+@pytest.mark.parametrize("m,n,k,ksplit", [(7, 100, 1234, 5), (160, 256, 5000, 39), (256, 64, 33, 1), (256, 64, 33, 5)])
 def test_linear_splitk(m, n, k, ksplit):
-    """skinny split-K linear (mlp_cond.0 at K = 5000) vs float64; ragged m / n / k and a padded x row stride"""
+    """skinny split-K linear (mlp_cond.0 at K = 5000) vs float64; ragged m / n / k and a padded x row stride; (256, 64, 33, 5):
+    K slices are 32 wide, so slices 2..4 of the 33 input features are empty"""
     L, lib = _lib()
     g = torch.Generator().manual_seed(9)
     x = torch.randn(m, k + 3, generator=g)
