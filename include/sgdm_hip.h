@@ -791,6 +791,28 @@ int sgd_lv_loss_bwd(const float* out, const float* x0, const float* noise, const
                     const float* wt, const float* gper_w /* DEVICE [b] */, const float* gper_vlb /* DEVICE [b] */, int32_t par,
                     int32_t kind, int32_t b, int32_t c, int32_t hw, float* gout /* [b, 2c, hw] */, void* stream);
 
+/* Guidance-distillation loss and its gradient (csrc/distill.hip; hparam distill_guidance, sgdm_amd/train.py; Meng et al. 2023,
+ * stage 1; additive entries, no counterpart in the reference): sgd_loss_fwd / sgd_loss_bwd with
+ *   target = guided(teach, cfg_mode, *w_dev)   -- 0: teach | 1 imagen: (1-w)*u + w*c | 2 cfg: (1+w)*c - w*u, each product rounded
+ *            before it is added: the bits of sgd_cfg_guide (rescale 0); never written to memory
+ * `out` is the student's output, NCHW [b, c, hw]; `teach` the teacher's RAW output as its engine leaves it, NHWC [2b, hw, c]
+ * ([cond ; uncond]) when cfg_mode != 0, else [b, hw, c] (e.g. sgd_cfg_guide's rescaled buffer); w_dev a DEVICE float[1] (may be
+ * NULL when cfg_mode == 0); t DEVICE int64 [b]; wt DEVICE fp32 [T] or NULL = 1.  kind, l, d, k and g as sgd_loss_fwd / _bwd.
+ * sgd_distill_loss_fwd: per_raw[n] = mean over c*hw of l, per_w[n] = wt[t[n]] * per_raw[n]; one workgroup per sample, per-thread
+ *   partial sums in double folded in a fixed order (identical from run to run, no atomics).
+ * sgd_distill_loss_bwd: gout [b, c, hw] = d (sum_n gper[n] * per_w[n]) / d out * gscale, element-wise; gper and the weight are
+ *   read from DEVICE memory and gscale is a constant of the caller: no by-value argument depends on the step.
+ * A thread owns pixels and loops over the channels (as sgd_v_to_eps); 16-byte accesses to out / gout when hw % 4 == 0 and both
+ * are 16-byte aligned, one float per lane otherwise.  SGD_ERR_ARG, nothing launched: b, c or hw <= 0, cfg_mode / kind out of
+ * range, a NULL pointer the call needs (w_dev when cfg_mode != 0). */
+int sgd_distill_loss_fwd(const float* out, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* t,
+                         const float* wt /* [T] or NULL = 1 */, int32_t kind, int32_t b, int32_t c, int32_t hw,
+                         float* per_raw /* [b] */, float* per_w /* [b] */, void* stream);
+int sgd_distill_loss_bwd(const float* out, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* t,
+                         const float* wt, int32_t kind, int32_t b, int32_t c, int32_t hw,
+                         const float* gper /* DEVICE [b]: dL / d per_w */, float gscale, float* gout /* [b, c, hw] */,
+                         void* stream);
+
 /* --------------------------------------------------------------------------------------
  * Optimizer step: AdamW (lightning_module_common.py:20-42: torch.optim.AdamW defaults, decoupled weight decay)
  * and the LitEma shadow update (dynamic/ema.py:25-44) of every parameter in ONE launch:

@@ -45,6 +45,9 @@ FILE_FLAGS["loss.hip"] = ["-ffp-contract=off"]
 # simple term carries sgd_loss_fwd's bits) and its ancestral update (sgd_ddpm_lv_step), product by product
 FILE_FLAGS["lvloss.hip"] = ["-ffp-contract=off"]
 FILE_FLAGS["lvstep.hip"] = ["-ffp-contract=off"]
+# distill.hip: the same -- the guided target of the distillation loss (sgd_distill_loss_fwd / sgd_distill_loss_bwd) carries the
+# bits of sgd_cfg_guide, product by product
+FILE_FLAGS["distill.hip"] = ["-ffp-contract=off"]
 
 
 def _sources():

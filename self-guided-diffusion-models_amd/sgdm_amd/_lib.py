@@ -174,6 +174,8 @@ SIGNATURES = {
     "sgd_lv_loss_fwd": (i32, [vp, vp, vp, vp, C.POINTER(LvTables), vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "sgd_lv_loss_bwd": (i32, [vp, vp, vp, vp, C.POINTER(LvTables), vp, dvp, dvp, i32, i32, i32, i32, i32, vp, vp]),
     "sgd_ddpm_lv_step": (i32, [vp, vp, vp, i32, f32, dvp, i32, i32, i32, i32, vp, vp, vp]),
+    "sgd_distill_loss_fwd": (i32, [vp, vp, i32, dvp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "sgd_distill_loss_bwd": (i32, [vp, vp, i32, dvp, vp, vp, i32, i32, i32, i32, dvp, f32, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

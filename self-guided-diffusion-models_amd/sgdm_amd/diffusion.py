@@ -28,6 +28,11 @@ Also without a counterpart, learned variance (Nichol & Dhariwal 2021): the hpara
 sgd_lv_loss_fwd / sgd_lv_loss_bwd), the 'native' update ``_LVUpdate`` (sgd_ddpm_lv_step) that samples with it, the sampling kwarg
 ``native_steps`` = K (``native_times``, ``native_rows``: a strided ancestral chain, fixed or learned variance), the C-row head of
 every other sampler (``_StepRunner.head``) and ``LatentDiffusion.calc_bpd``.
+Also without a counterpart, guidance distillation (Meng et al. 2023, stage 1): the hparams ``distill_guidance`` = w /
+``distill_rescale`` = phi (``distill_option``) and ``LatentDiffusion.set_distill_teacher`` make ``train.p_losses_hip`` train the
+conditional evaluation against the teacher's guided output (include/sgdm_hip.h: sgd_distill_loss_fwd / sgd_distill_loss_bwd); the
+sampling kwarg ``cfg_distilled`` (hparam ``guidance_distilled``) samples such a student with ONE evaluation at B per step, on the
+captured step the batch-B graph alone (``_GraphedStep``: no 2B engine is built).
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -122,6 +127,23 @@ def loss_weighting_option(h):
     if not (np.abs(table) <= np.finfo(np.float32).max).all() or (table < 0).any():          # (NaN fails the comparison)
         raise ValueError("loss_weighting_table must hold finite (in fp32), non-negative weights")
     return scheme, gamma, k, table
+
+
+def distill_option(h):
+    """the optional hparams ``distill_guidance`` = w (None / absent: off; the guidance weight the student is trained to
+    reproduce, in the teacher's own scale type) and ``distill_rescale`` = phi in [0, 1] (0 / absent: off; CFG rescale, Lin et
+    al. 2023, applied to the target), validated: None when off, else (w, phi).  Pure host code."""
+    w, phi = getattr(h, "distill_guidance", None), getattr(h, "distill_rescale", None)
+    if w is None:
+        if phi is not None:
+            raise ValueError("distill_rescale is given but distill_guidance is not")
+        return None
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not np.isfinite(w):
+        raise ValueError(f"distill_guidance={w!r} must be a finite number (the teacher's guidance weight), or None")
+    phi = 0.0 if phi is None else phi
+    if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:      # (NaN fails the comparison)
+        raise ValueError(f"distill_rescale={phi!r}: a number in [0, 1]")
+    return float(w), float(phi)
 
 
 def loss_weight_table(alphas_cumprod_fp32, parameterization, scheme, gamma=5.0, k=1.0):
@@ -220,8 +242,21 @@ def cfg_options(sk, fused=True):
     """(cfg_rescale, cfg_interval) of the sampling kwargs: phi in [0, 1] (0: off) and ``(t_lo, t_hi)`` in training timesteps,
     inclusive (None: guidance on every evaluation).  ValueError for a value out of range and, with an option set, for a step
     that is not the fused-CFG one (``fused``: _StepRunner.fused_cfg()) -- the guide pass works on the two halves of the doubled
-    evaluation.  Pure host code: no device, no library."""
+    evaluation.  The sampling kwarg ``cfg_distilled`` (a guidance-distilled student: every evaluation the conditional one at
+    B) is refused with either option -- there is no second half to guide or rescale with --, with the learned-variance
+    'native' update and on a step that is not the drop-in UNet's.  Pure host code: no device, no library."""
     sk = sk or {}
+    if cfg_distilled_option(sk):
+        if sk.get("cfg_interval") is not None or sk.get("cfg_rescale", 0) != 0:
+            raise ValueError("cfg_distilled with cfg_interval / cfg_rescale: a distilled student has one (conditional) "
+                             "evaluation per step, there is no guidance to schedule or rescale")
+        if sk.get("lv_native", False):
+            raise ValueError("cfg_distilled with the learned-variance 'native' update: distillation of learned-variance "
+                             "models is not implemented")
+        if not fused:
+            raise ValueError("cfg_distilled needs the drop-in UNet's forward_with_cond_scale as denoise_sample_fn (and no p0): "
+                             "a generic denoise_sample_fn guides inside the call")
+        return 0.0, None
     phi, iv = sk.get("cfg_rescale", 0), sk.get("cfg_interval")
     if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:       # (NaN fails the comparison)
         raise ValueError(f"cfg_rescale={phi!r}: a number in [0, 1]")
@@ -235,6 +270,14 @@ def cfg_options(sk, fused=True):
         raise ValueError("cfg_rescale / cfg_interval need the fused-CFG step: the drop-in UNet's forward_with_cond_scale, a "
                          "numeric cond_scale that is not its single-evaluation 0 / 1 shortcut, and no p0")
     return float(phi), iv
+
+
+def cfg_distilled_option(sk):
+    """the sampling kwarg ``cfg_distilled`` (default False), a bool.  Pure host code."""
+    on = (sk or {}).get("cfg_distilled", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"cfg_distilled={on!r} (True or False)")
+    return bool(on)
 
 
 V_FORM_SAMPLERS = ("native", "ddim", "dpmsolver")
@@ -371,12 +414,14 @@ class _StepRunner:
     guide pass (sgd_cfg_guide) behind the UNet and everything after it reads the guided buffer with mode 0; an evaluation
     outside the interval is ONE UNet evaluation at B, nothing dropped.  On the data form of 'v' (``form`` 'data') there is no
     v -> eps pass: ``eps`` returns the network output (or the guided buffer) as it is and the update (_VUpdate, sgd_v_step)
-    takes the UNet's time and the two schedule tables, one launch fewer per evaluation"""
+    takes the UNet's time and the two schedule tables, one launch fewer per evaluation.  With ``cfg_distilled`` in ``sk``
+    (``distilled``: a guidance-distilled student) EVERY evaluation is that one evaluation at B and ``cond_scale`` is not read"""
 
     def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
         self.fn = denoise_sample_fn
         self.kwargs = dict(kwargs)
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
+        self.distilled = cfg_distilled_option(sk)
         self.rescale, self.interval = cfg_options(sk, self.fused_cfg())        # refused before anything is loaded or launched
         self.scheduled = self.rescale > 0 or self.interval is not None
         # 'data' (sampling kwarg v_form, checked by the sampler: v_form_option): no v -> eps pass, the update reads v itself
@@ -414,6 +459,8 @@ class _StepRunner:
         """whether a step takes the batch-doubled evaluation whose guided score is formed inside the step kernel: the
         drop-in UNet, a numeric guidance weight that is not the model kind's single-evaluation 0 / 1 shortcut, no ``p0``"""
         m, w = self.model, self.kwargs.get("cond_scale")
+        if self.distilled:                          # the same step with its conditional evaluation alone, whatever the weight
+            return m is not None and self.kwargs.get("p0") is None
         if m is None or not isinstance(w, (int, float)) or self.kwargs.get("p0") is not None:
             return False
         fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else True
@@ -452,7 +499,7 @@ class _StepRunner:
         m = self.model
         if self.fused_cfg():
             kw = self.kwargs
-            if self.scheduled and not guided:
+            if self.distilled or (self.scheduled and not guided):
                 # the conditional prediction alone: one evaluation at B, RNG consumed as forward(cond_drop_prob=p0) does
                 mask = m._draw_mask(B, 0.0, x.device) if self.cond_only_mask() else None
                 eng, mode, w = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B, self.head(Cc)), 0, 0.0
@@ -674,6 +721,8 @@ class _GraphedStep:
     bounds are data, not part of the capture.  With an interval requested the step holds TWO graphs over the same static
     buffers and the same update object: ``graph`` (2B engine, guide pass) and ``graph1`` (the engine at B, conditional
     prediction alone); ``step`` replays one or the other by the host table ``begin`` built, and counts them in ``replays``.
+    A distilled step (sampling kwarg cfg_distilled) holds ``graph1`` alone: the engine at B is its only engine, no 2B engine
+    or workspace exists for it, and every replay counts as 'cond'.
     """
 
     MAX_PER_ENGINE = 8          # captured steps kept per (model, batch, resolution, precision) engine
@@ -687,15 +736,18 @@ class _GraphedStep:
         sig = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         prec = L.PREC_BY_NAME[m.hip_precision]
         # (a learned-variance model under an update that ignores the variance half: the engine with the C-row head)
-        eng = m._engine(2 * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]))
+        # (a distilled student, sampling kwarg cfg_distilled: the engine at B is the step's only one -- the 2B engine and its
+        # workspace are never built)
+        eng = m._engine((1 if runner.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]))
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
         # (the data form of 'v' captures another update launch and no conversion: a third kind of entry)
         par = "eps" if runner.v is None else ("v", runner.v[0].numel()) + (("data",) if runner.form == "data" else ())
         # a scheduled step reads its weight from the device: a sweep over weights or intervals reuses one capture (a pair
         # of graphs, when an interval is requested, is one entry)
-        w = None if runner.scheduled else float(kw["cond_scale"])
+        w = None if runner.scheduled or runner.distilled else float(kw["cond_scale"])
         key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, m._scale_mode(), sig(cond), sig(layout), par,
-               (runner.rescale, runner.interval is not None), (runner.lv, runner.head(img.shape[1]), upd.native_steps))
+               (runner.rescale, runner.interval is not None), (runner.lv, runner.head(img.shape[1]), upd.native_steps),
+               runner.distilled)
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
         if g is None:                                       # the key covers all of ``upd`` that the capture baked in
@@ -726,13 +778,15 @@ class _GraphedStep:
         self.cond = None if c0 is None else (c0.detach().clone() if c0.dtype == torch.int64 else c0.detach().float().clone()).contiguous()
         self.layout = None if l0 is None else (l0.detach().clone() if l0.dtype in (torch.uint8, torch.int32, torch.int64)
                                                else l0.detach().float().clone()).contiguous()
-        self.has_mask, self.p = runner.drop_mask(B, dev)
-        self.u = torch.zeros(2 * B, device=dev)
-        self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
-        eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
-        self._inputs = eng._keep_inputs                 # the captured launches read these buffers on every replay
+        self.distilled = runner.distilled               # ``eng`` is the engine at B and ``graph1`` the only graph
         img = self.img
-        w, mode = float(kw["cond_scale"]), m._scale_mode()
+        if not self.distilled:
+            self.has_mask, self.p = runner.drop_mask(B, dev)
+            self.u = torch.zeros(2 * B, device=dev)
+            self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
+            eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
+            self._inputs = eng._keep_inputs             # the captured launches read these buffers on every replay
+            w, mode = float(kw["cond_scale"]), m._scale_mode()
         # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
         self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
         data = runner.form == "data"                    # the update reads v itself, at the static t, from the static tables
@@ -760,12 +814,12 @@ class _GraphedStep:
                 return tail(st, runner.guide(eng.eps_nhwc, mode, self.w, B, Cc, hw, self.g, st), 0, 0.0)
             tail(st, eng.eps_nhwc, mode, w)
 
-        self.graph = self._capture(eng, guided_step, dev)
+        self.graph = None if self.distilled else self._capture(eng, guided_step, dev)
         self.eng1 = self.graph1 = self.u1 = None
-        if runner.interval is not None:
+        if runner.interval is not None or self.distilled:
             # the conditional prediction alone: the engine at B over the same img / t / cond / layout; its mask stays all-false
             # (``u1`` is only drawn into, to consume the RNG like the model's own single evaluation)
-            eng1 = self.eng1 = m._engine(B, img.shape[2], img.shape[3], eng.prec, runner.head(Cc))
+            eng1 = self.eng1 = eng if self.distilled else m._engine(B, img.shape[2], img.shape[3], eng.prec, runner.head(Cc))
             self.u1 = torch.zeros(B, device=dev) if runner.cond_only_mask() else None
             self.mask1 = torch.zeros(B, dtype=torch.bool, device=dev) if runner.cond_only_mask() else None
             eng1.prepare(img, self.t, self.cond, self.layout, self.mask1)
@@ -799,7 +853,7 @@ class _GraphedStep:
         schedule row; scheduled: whether each evaluation is guided, and its weight) and, for parameterization 'v', the two
         schedule tables into device buffers; packed weights re-checked"""
         self.eng.refresh(torch.cuda.current_stream().cuda_stream)
-        if self.eng1 is not None:
+        if self.eng1 is not None and self.eng1 is not self.eng:
             self.eng1.refresh(torch.cuda.current_stream().cuda_stream)
         self.img.copy_(img)
         if self.cond is not None:
@@ -817,7 +871,7 @@ class _GraphedStep:
 
     def step(self, i, noise=None, want_x0=True):
         """schedule row i; draws the mask uniform and z like the eager step (``x0`` is written on every replay)"""
-        guided = self.flags is None or self.flags[i]
+        guided = not self.distilled and (self.flags is None or self.flags[i])
         if not guided:
             if self.u1 is not None:
                 self.u1.uniform_(0, 1)                  # the B-long draw of forward(cond_drop_prob=p0); nothing is dropped
@@ -1524,6 +1578,9 @@ class LatentDiffusion(nn.Module):
         self.hparams = _Obj(kwargs)
         self.sampler = Schedule_DDPM(**kwargs)
         h = self.hparams
+        # optional hparams (not in the reference; Meng et al. 2023, stage 1): the training target is the guided output of a
+        # frozen teacher (set_distill_teacher; sgdm_amd/train.py)
+        self.distill = distill_option(h)
         self.sampler_list = {
             "native": self.sampler,
             "ddim": DDIMSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device, sampler_type="ddim"),
@@ -1545,6 +1602,15 @@ class LatentDiffusion(nn.Module):
 
         _denoise_sample_fn._sgdm_inner = denoise_sample_fn
         self.denoise_sample_fn = _denoise_sample_fn
+
+    def set_distill_teacher(self, teacher):
+        """the frozen teacher of guidance distillation (hparam distill_guidance): a drop-in UNet (sgdm_amd.train.
+        distill_teacher_from; on the device its doubled evaluation feeds the fused loss kernels) or any callable
+        ``teacher(x, t, cond_scale, **cond_kwargs)`` with forward_with_cond_scale semantics.  It is NOT registered as a
+        submodule: it reaches no parameters(), state_dict(), optimizer, EMA or gradient exchange, and follows no .to() /
+        .train() of this module.  None removes it."""
+        object.__setattr__(self, "_distill_teacher", teacher)
+        self.__dict__.pop("_distill_runner", None)
 
     def forward_tao(self, x, **kwargs):
         return self.forward(x, **kwargs)
@@ -1599,6 +1665,8 @@ class LatentDiffusion(nn.Module):
             if self.sampler.zero_terminal_snr and sampling_method in V_FORM_SAMPLERS and not (
                     self.sampler.learn_sigma and sampling_method == "native"):
                 sk.setdefault("v_form", "data")
+        if getattr(self.hparams, "guidance_distilled", False):      # a distilled student: one conditional evaluation per step
+            sk.setdefault("cfg_distilled", True)
         native_steps_option(sk, sampling_method, self.hparams.num_timesteps)     # refused on every other sampler
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(

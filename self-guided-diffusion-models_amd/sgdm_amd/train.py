@@ -17,7 +17,10 @@ walking the forward tape in reverse:
   * with the hparam ``loss_weighting`` (not in the reference): the per-timestep weighted loss and its gradient =
     ``sgd_loss_fwd`` / ``sgd_loss_bwd`` (``_WeightedLossFn``), the target formed on the fly;
   * with the hparam ``learn_sigma`` (not in the reference): the hybrid loss L_simple + vlb_weight * L_vlb of a 2C-wide model
-    output and its gradient = ``sgd_lv_loss_fwd`` / ``sgd_lv_loss_bwd`` (``_LVLossFn``).
+    output and its gradient = ``sgd_lv_loss_fwd`` / ``sgd_lv_loss_bwd`` (``_LVLossFn``);
+  * with the hparam ``distill_guidance`` (not in the reference; Meng et al. 2023, stage 1): the loss against the guided output
+    of a frozen teacher and its gradient = ``sgd_distill_loss_fwd`` / ``sgd_distill_loss_bwd`` (``_DistillLossFn``), the target
+    formed on the fly from the raw output the teacher's doubled evaluation left in its engine.
 
 ``loss.backward()`` works because the UNet evaluation is a ``torch.autograd.Function`` whose inputs are the
 trainable parameters; it returns one gradient tensor per parameter in the reference layout.
@@ -1055,6 +1058,136 @@ class _WeightedLossFn(torch.autograd.Function):
         return (gout,) + (None,) * 8
 
 
+# ---- guidance distillation (hparam distill_guidance; Meng et al. 2023, stage 1): the target is the guided output of a frozen
+# teacher, in the model's own output space (guidance is linear in it, so every parameterization works unchanged).
+class _DistillLossFn(torch.autograd.Function):
+    """(per_w, per_raw) = per-sample loss of the student's output against guided(teacher's raw output), with and without the
+    timestep weight, one launch (sgd_distill_loss_fwd); the gradient for the student's output in one more
+    (sgd_distill_loss_bwd).  ``teach`` is the teacher engine's own output buffer ([2B, hw, C], or the guide pass's [B, hw, C]
+    with mode 0) read in place by both kernels: the target is never written, nothing is re-laid.  The backward reads the buffer
+    again, so it must run before the teacher's next evaluation at this batch -- the order of every training loop, and the rule
+    the student's own backward already imposes (_UNetTrainFn)."""
+
+    @staticmethod
+    def forward(ctx, out, teach, mode, w_dev, t, wt, kind):
+        lib = L.load()
+        out = out.contiguous().float()
+        B, Cc, hw = out.shape[0], out.shape[1], out[0, 0].numel()
+        per_raw, per_w = (torch.empty(B, dtype=torch.float32, device=out.device) for _ in range(2))
+        L.check(lib.sgd_distill_loss_fwd(_ptr(out), _ptr(teach), mode, _ptr(w_dev), _ptr(t), _ptr(wt), kind, B, Cc, hw,
+                                         _ptr(per_raw), _ptr(per_w), torch.cuda.current_stream().cuda_stream),
+                "sgd_distill_loss_fwd")
+        ctx.save_for_backward(out, teach, w_dev, t, wt)
+        ctx.mode, ctx.kind = mode, kind
+        ctx.mark_non_differentiable(per_raw)
+        return per_w, per_raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, _graw):
+        out, teach, w_dev, t, wt = ctx.saved_tensors
+        gper = gper.contiguous().float()
+        gout = torch.empty_like(out)
+        L.check(L.load().sgd_distill_loss_bwd(_ptr(out), _ptr(teach), ctx.mode, _ptr(w_dev), _ptr(t), _ptr(wt), ctx.kind,
+                                              out.shape[0], out.shape[1], out[0, 0].numel(), gper.data_ptr(), 1.0, _ptr(gout),
+                                              torch.cuda.current_stream().cuda_stream), "sgd_distill_loss_bwd")
+        return (gout,) + (None,) * 6
+
+
+def distill_teacher_from(model, ema=None, hip_precision=None):
+    """a frozen teacher for guidance distillation from a drop-in UNet: a deep copy of ``model`` (parameters and buffers; no
+    engine, workspace or captured step is copied -- the teacher builds its own), with the EMA shadows copied in when ``ema``
+    (a LitEma of ``model``) is given, in eval mode with nothing requiring grad, and optionally another arithmetic mode
+    (``hip_precision``).  The inference-only modes 'f16' / 'bf16' are allowed: the teacher only ever runs under
+    torch.no_grad().  Hand the result to ``LatentDiffusion.set_distill_teacher``."""
+    import copy
+    from .unet import UNetModelBase
+    if not isinstance(model, UNetModelBase):
+        raise TypeError(f"distill_teacher_from copies a drop-in UNet, not {type(model).__name__}")
+    if hip_precision is not None and hip_precision not in L.PREC_BY_NAME:
+        raise ValueError(f"hip_precision={hip_precision!r}: one of {sorted(L.PREC_BY_NAME)}")
+    # what belongs to ``model``'s device state stays behind: the copy starts with empty caches
+    memo = {id(model.__dict__[k]): {} for k in ("_engines", "_hip_graph_steps") if k in model.__dict__}
+    # (the ``condition`` node of the config is read only and shared: attribute-style dict classes often cannot be deep-copied)
+    memo[id(model.condition)] = model.condition
+    teacher = copy.deepcopy(model, memo)
+    teacher._engines = {}
+    teacher.__dict__.pop("_hip_graph_steps", None)
+    teacher.__dict__.pop("_tensor_list", None)
+    if ema is not None:
+        ema.copy_to(teacher)                    # (the copy still has ``model``'s requires_grad flags, which name the shadows)
+    teacher.eval().requires_grad_(False)
+    if hip_precision is not None:
+        teacher.hip_precision = hip_precision
+    return teacher
+
+
+def _distill_setup(diff, student, kwargs, device):
+    """the checks of a distillation step, all before anything is launched: (w, phi, teacher UNet or None, teacher callable).
+    ``student``: the UNet behind denoise_fn when it is one.  ValueError: no teacher; learned variance on either model;
+    out_channels that differ; teacher and student the same object; a teacher that is in train mode or has parameters that
+    require grad; a caller's cond_drop_mask (the student is trained on its conditional branch alone); distill_rescale off
+    the fused path (the rescale needs both halves of the teacher's doubled evaluation)."""
+    from .unet import UNetModelBase
+    w, phi = diff.distill
+    teacher = getattr(diff, "_distill_teacher", None)
+    if teacher is None:
+        raise ValueError("distill_guidance is set but there is no teacher: call set_distill_teacher(teacher) first "
+                         "(sgdm_amd.train.distill_teacher_from copies one from a drop-in UNet)")
+    owner = getattr(teacher, "__self__", teacher)
+    if owner is student or teacher is diff.denoise_fn or owner is diff.denoise_fn:
+        raise ValueError("distillation: teacher and student are the same object; the teacher must be a frozen copy "
+                         "(sgdm_amd.train.distill_teacher_from)")
+    if getattr(diff.sampler, "learn_sigma", False) or getattr(owner, "learn_sigma", False):
+        raise ValueError("distillation of learned-variance models (learn_sigma) is not implemented")
+    oc_t, oc_s = getattr(owner, "out_channels", None), getattr(student, "out_channels", None)
+    if oc_t is not None and oc_s is not None and oc_t != oc_s:
+        raise ValueError(f"distillation: the teacher has {oc_t} output channels, the student {oc_s}")
+    if isinstance(owner, torch.nn.Module):
+        if owner.training:
+            raise ValueError("distillation: the teacher is in train mode; call teacher.eval() (dropout must be off)")
+        if any(p.requires_grad for p in owner.parameters()):
+            raise ValueError("distillation: the teacher has parameters that require grad; call teacher.requires_grad_(False)")
+    if kwargs.get("cond_drop_mask") is not None:
+        raise ValueError("distillation trains the student's conditional evaluation alone (cond_drop_prob is forced to 0): "
+                         "a cond_drop_mask cannot be honoured")
+    unet = owner if isinstance(owner, UNetModelBase) and device.type == "cuda" else None
+    if unet is not None and getattr(teacher, "__name__", "forward_with_cond_scale") != "forward_with_cond_scale":
+        unet = None                                 # some other bound method of a UNet: called as it is
+    if phi > 0 and unet is None:
+        raise ValueError("distill_rescale needs the fused path: a drop-in UNet teacher on the device (the rescale reads both "
+                         "halves of its doubled evaluation)")
+    fn = teacher if owner is not teacher or not hasattr(teacher, "forward_with_cond_scale") else teacher.forward_with_cond_scale
+    return w, phi, unet, fn
+
+
+def _distill_teacher_eval(diff, unet, w, phi, x_noisy, t, kwargs):
+    """the fused path: the teacher's doubled evaluation under no_grad, its raw output left where the engine wrote it.
+    Returns (teach buffer, cfg_mode, device float w): ``eng.eps_nhwc`` [2B, hw, C] with the teacher's scale type, or with
+    distill_rescale the guide pass's [B, hw, C] and mode 0."""
+    from .diffusion import _StepRunner
+    runner = diff.__dict__.get("_distill_runner")
+    if runner is None or runner.model is not unet:
+        runner = diff.__dict__["_distill_runner"] = _StepRunner(unet.forward_with_cond_scale, dict(cond_scale=w))
+        runner.w_dev = {}
+    dev = x_noisy.device
+    if dev not in runner.w_dev:
+        runner.w_dev[dev] = torch.full((1,), w, dtype=torch.float32, device=dev)
+    w_dev = runner.w_dev[dev]
+    B, Cc, hw = x_noisy.shape[0], x_noisy.shape[1], x_noisy[0, 0].numel()
+    with torch.no_grad():
+        has_mask, p = runner.drop_mask(B, dev)      # [never | always]: rows [0, B) conditional, [B, 2B) dropped
+        mask = unet._draw_mask(2 * B, p, dev) if has_mask else None
+        eng = unet._run(x_noisy, t, kwargs.get("cond"), kwargs.get("layout"), mask, 2 * B)
+        teach, mode = eng.eps_nhwc, unet._scale_mode()
+        if phi > 0:
+            g = torch.empty((B, hw, Cc), device=dev)
+            L.check(runner.lib.sgd_cfg_guide(_ptr(teach), mode, _ptr(w_dev), phi, B, Cc, hw, _ptr(g),
+                                             torch.cuda.current_stream().cuda_stream), "sgd_cfg_guide")
+            teach, mode = g, 0
+    return teach, mode, w_dev
+
+
 # ---- learned variance (hparam learn_sigma; Nichol & Dhariwal 2021): L_simple + vlb_weight * L_vlb.  The torch chain below is
 # the CPU branch of p_losses and the restatement the device kernels (csrc/lvloss.hip) are tested against; it runs in the
 # dtype of its inputs (float64 for gradcheck), except the decoder term, which is always evaluated in double.
@@ -1237,11 +1370,26 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     # hparam learn_sigma: the output is 2C wide and the loss is L_simple + vlb_weight * L_vlb (lv_loss); its kernels form
     # the target themselves, like the weighted ones
     lv = getattr(s, "learn_sigma", False)
+    # hparam distill_guidance: the target is the guided output of the frozen teacher, in the model's own output space; the
+    # student is trained on its conditional evaluation alone (cond_drop_prob forced to 0).  Everything is checked here,
+    # before the first launch.  On the device, with a drop-in UNet teacher, the loss kernels read the teacher's raw output
+    # in place (_DistillLossFn); anywhere else the target is a tensor and the chain below runs unchanged on it.
+    dist = getattr(diff, "distill", None)
+    d_teach = d_target = None
+    if dist is not None:
+        d_w, d_phi, d_unet, d_fn = _distill_setup(diff, fn, kwargs, x_start.device)
+        if h.loss_type not in _LOSS_KIND:
+            raise NotImplementedError(f"unknown loss type '{h.loss_type}'")
+        if d_unet is not None and d_unet.out_channels != x_start.shape[1]:
+            raise ValueError(f"distillation: the teacher has {d_unet.out_channels} output channels, the image {x_start.shape[1]}")
+        kwargs = dict(kwargs, cond_drop_prob=0.0)
+        fused = False                   # (the weighted kernels form the trained target themselves: not this one)
     if x_start.device.type == "cuda":
         x_noisy = torch.empty_like(x_start)
         B = x_start.shape[0]
         x0, nz, tt = x_start.contiguous().float(), noise.contiguous().float(), t.contiguous().to(torch.int64)
-        if h.parameterization == "v" and not fused and not lv:   # x_noisy and the target from one read of x_start and noise
+        if h.parameterization == "v" and not fused and not lv and dist is None:
+            # x_noisy and the target from one read of x_start and noise
             v_target = torch.empty_like(x_start)
             L.check(lib.sgd_q_sample_v(_ptr(x0), _ptr(nz), _ptr(tt), _ptr(s.sqrt_alphas_cumprod),
                                        _ptr(s.sqrt_one_minus_alphas_cumprod), B, x0[0].numel(), _ptr(x_noisy), _ptr(v_target),
@@ -1252,13 +1400,25 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
                                      torch.cuda.current_stream().cuda_stream), "sgd_q_sample")
     else:
         x_noisy = s.q_sample(original_sample=x_start, t=t, noise=noise)
-        if h.parameterization == "v":
+        if h.parameterization == "v" and dist is None:
             v_target = (s._ext(s.sqrt_alphas_cumprod, t, x_start.shape) * noise
                         - s._ext(s.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start)
+    if dist is not None:
+        if d_unet is not None:          # the doubled evaluation; the raw output stays in the teacher's engine
+            d_teach = _distill_teacher_eval(diff, d_unet, d_w, d_phi, x_noisy, tt, kwargs)
+        else:
+            with torch.no_grad():
+                ckw = {k: kwargs[k] for k in ("layout",) if k in kwargs}
+                d_target = d_fn(x_noisy, t, d_w, cond=kwargs.get("cond"), **ckw).detach()
     model_output, loss_inside, dict_inside = diff.denoise_fn(x_noisy, t, *args, **kwargs)
     prefix = "train" if diff.training else "val"
     loss_dict = {f"{prefix}/{k}": v for k, v in dict_inside.items()}
-    if h.parameterization == "x0":
+    if dist is not None:
+        target = d_target               # (None on the fused path: the kernels form it)
+        if d_target is not None and d_target.shape != model_output.shape:
+            raise ValueError(f"distillation: the teacher's output is {tuple(d_target.shape)}, the student's "
+                             f"{tuple(model_output.shape)}")
+    elif h.parameterization == "x0":
         target = x_start
     elif h.parameterization == "eps":
         target = noise
@@ -1271,6 +1431,12 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
         loss, raw_lv, vlb = lv_loss(s, h, model_output, x0 if on_dev else x_start, nz if on_dev else noise,
                                     tt if on_dev else t, weights)
         raw = raw_lv if weights is not None else None
+    elif d_teach is not None:
+        if model_output.shape != x_start.shape:
+            raise ValueError(f"distillation: the student's output is {tuple(model_output.shape)}, the image "
+                             f"{tuple(x_start.shape)}")
+        loss, raw_d = _DistillLossFn.apply(model_output, *d_teach, tt, weights, _LOSS_KIND[h.loss_type])
+        raw = raw_d if weights is not None else None
     elif fused:
         loss, raw = _WeightedLossFn.apply(model_output, x0, nz, tt, s.sqrt_alphas_cumprod, s.sqrt_one_minus_alphas_cumprod,
                                           weights, _LOSS_PAR[h.parameterization], _LOSS_KIND[h.loss_type])
