@@ -751,7 +751,7 @@ int sgd_loss_bwd(const float* out, const float* x0, const float* noise, const in
                  const float* sqrt_1mac, const float* wt, const float* gper /* DEVICE [b]: dL / d per_w */, float gscale,
                  int32_t par, int32_t kind, int32_t b, int64_t chw, float* gout /* [b, chw] */, void* stream);
 
-/* Hybrid loss of a learned-variance model, L_simple + lambda L_vlb (csrc/lvloss.hip; hparam learn_sigma, sgdm_amd/train.py;
+/* Hybrid loss of a learned-variance model, L_simple + lambda L_vlb (csrc/lvloss.hip; hparam learn_sigma, sgdm_amd/losses.py;
  * Nichol & Dhariwal 2021; additive entries, no counterpart in the reference).  out is the model output NCHW [b, 2c, hw]:
  * m = out[:, :c] predicts the trained target, v = out[:, c:] interpolates the log-variance; x0, noise NCHW [b, c, hw]; t DEVICE
  * int64 [b]; `tables` is a HOST struct of DEVICE fp32 [T] tables (sqrt_recip_ac / sqrt_recipm1_ac may be NULL unless par 0).
@@ -791,7 +791,7 @@ int sgd_lv_loss_bwd(const float* out, const float* x0, const float* noise, const
                     const float* wt, const float* gper_w /* DEVICE [b] */, const float* gper_vlb /* DEVICE [b] */, int32_t par,
                     int32_t kind, int32_t b, int32_t c, int32_t hw, float* gout /* [b, 2c, hw] */, void* stream);
 
-/* Guidance-distillation loss and its gradient (csrc/distill.hip; hparam distill_guidance, sgdm_amd/train.py; Meng et al. 2023,
+/* Guidance-distillation loss and its gradient (csrc/distill.hip; hparam distill_guidance, sgdm_amd/losses.py; Meng et al. 2023,
  * stage 1; additive entries, no counterpart in the reference): sgd_loss_fwd / sgd_loss_bwd with
  *   target = guided(teach, cfg_mode, *w_dev)   -- 0: teach | 1 imagen: (1-w)*u + w*c | 2 cfg: (1+w)*c - w*u, each product rounded
  *            before it is added: the bits of sgd_cfg_guide (rescale 0); never written to memory

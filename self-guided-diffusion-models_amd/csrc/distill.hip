@@ -3,8 +3,9 @@
 // (gfx950; include/sgdm_hip.h: sgd_distill_loss_fwd, sgd_distill_loss_bwd).  Per element
 //   target = guided(teach, cfg_mode, *w_dev)     (csrc/sampler_common.h: the form the step kernels and sgd_cfg_guide use)
 //   d = out - target;   l = d * d (kind 0) | |d| (kind 1) | |d| < 1 ? 0.5 * d * d : |d| - 0.5 (kind 2, smooth_l1 with beta 1)
-// i.e. sgd_loss_fwd / sgd_loss_bwd (csrc/loss.hip) with another target.  The target is formed on the fly in both passes from the
-// teacher's RAW output where its engine left it: no target tensor is written, nothing is re-laid.
+// i.e. sgd_loss_fwd / sgd_loss_bwd (csrc/loss.hip) with another target: loss_elem / loss_grad are csrc/loss_common.h's.  The
+// target is formed on the fly in both passes from the teacher's RAW output where its engine left it: no target tensor is
+// written, nothing is re-laid.
 //
 // Layouts: `out` / `gout` are the student's, hw-major (NCHW [b, c, hw]); `teach` is the teacher engine's, c-minor ([2b, hw, c],
 // [cond ; uncond], or [b, hw, c] with cfg_mode 0).  As in sgd_v_to_eps (csrc/vpred.hip) a thread owns PIXELS and loops over the
@@ -17,103 +18,67 @@
 //
 // Both passes are HBM-bound and small (3 * b * c * hw floats).  The forward is one workgroup per sample with one barrier,
 // like sgd_loss_fwd, and like it is deliberately not split over several workgroups (a second launch or atomics).
+#include "loss_common.h"
 #include "sampler_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
 
-constexpr int DISTILL_THREADS = 1024;               // forward: one workgroup per sample, 16 waves
-constexpr int DISTILL_WAVES = DISTILL_THREADS / 64;
-
-__device__ __forceinline__ float distill_elem(int kind, float d) {
-    if (kind == 0) return d * d;
-    const float ad = fabsf(d);
-    if (kind == 1) return ad;
-    return ad < 1.f ? 0.5f * d * d : ad - 0.5f;
-}
-
-// d l / d d times k (k: the sample's upstream factor; 2 * k is exact) -- csrc/loss.hip: loss_grad
-__device__ __forceinline__ float distill_grad(int kind, float d, float k) {
-    if (kind == 0) return (2.f * k) * d;
-    if (kind == 1) return k * (d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f);
-    return k * fminf(fmaxf(d, -1.f), 1.f);
-}
-
-// VEC: hw % 4 == 0 and `out` 16-byte aligned (then every channel plane starts on a 16-byte boundary): a thread owns four
-// consecutive pixels and reads them from a plane in one 16-byte access.  Otherwise one pixel per thread.  The teacher is read
-// float by float either way (a thread's 4 * c floats are consecutive; the c iterations use every byte of the lines they touch).
-// Per-thread partial sums in double (the fp32 value l of an element is exact in it), xor-shuffles inside each wave, one LDS slot
-// per wave, folded in ascending order by thread 0: no atomics, the result depends on the inputs alone.
-template <bool VEC>
-__global__ __launch_bounds__(DISTILL_THREADS) void distill_fwd_kernel(const float* __restrict__ out, const float* __restrict__ teach,
-                                                                      int cfg_mode, const float* __restrict__ w_dev,
-                                                                      const int64_t* __restrict__ t, const float* __restrict__ wt,
-                                                                      int kind, int b, int c, int hw,
-                                                                      float* __restrict__ per_raw, float* __restrict__ per_w) {
-    __shared__ double red[DISTILL_WAVES];
+// W == 4: hw % 4 == 0 and `out` 16-byte aligned (then every channel plane starts on a 16-byte boundary): a thread owns four
+// consecutive pixels and reads them from a plane in one 16-byte access.  W == 1: one pixel per thread.  The teacher is read
+// float by float either way (a thread's W * c floats are consecutive; the c iterations use every byte of the lines they touch).
+// Summed as loss_block_sum (csrc/loss_common.h).
+template <int W>
+__global__ __launch_bounds__(LOSS_FWD_THREADS) void distill_fwd_kernel(const float* __restrict__ out, const float* __restrict__ teach,
+                                                                       int cfg_mode, const float* __restrict__ w_dev,
+                                                                       const int64_t* __restrict__ t, const float* __restrict__ wt,
+                                                                       int kind, int b, int c, int hw,
+                                                                       float* __restrict__ per_raw, float* __restrict__ per_w) {
+    __shared__ double red[LOSS_FWD_THREADS / 64];
     const int n = blockIdx.x;
     const float w = cfg_mode ? *w_dev : 0.f;
     const float* __restrict__ o_n = out + (long)n * c * hw;
     double acc = 0.0;
-    if (VEC) {
-        for (int q = threadIdx.x; q < hw / 4; q += DISTILL_THREADS) {
-            const int p = 4 * q;
-            for (int cc = 0; cc < c; ++cc) {
-                const f32x4 o = *reinterpret_cast<const f32x4*>(o_n + (long)cc * hw + p);
+    for (int u = threadIdx.x; u < hw / W; u += LOSS_FWD_THREADS) {
+        const int p = W * u;
+        for (int cc = 0; cc < c; ++cc) {
+            const loss_vec<W> o = loss_load<W>(o_n, (long)cc * hw + p);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc += (double)distill_elem(kind, o[j] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p + j));
-            }
+            for (int j = 0; j < W; ++j) acc += (double)loss_elem(kind, o[j] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p + j));
         }
-    } else {
-        for (int p = threadIdx.x; p < hw; p += DISTILL_THREADS)
-            for (int cc = 0; cc < c; ++cc)
-                acc += (double)distill_elem(kind, o_n[(long)cc * hw + p] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p));
     }
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double s = loss_block_sum<LOSS_FWD_THREADS>(acc, red);
     if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int i = 0; i < DISTILL_WAVES; ++i) s += red[i];
         const float raw = (float)(s / ((double)c * (double)hw));
         per_raw[n] = raw;
         per_w[n] = wt ? wt[t[n]] * raw : raw;
     }
 }
 
-// element-wise over [b, c, hw]: `bps` blocks of 256 threads per sample, a thread per pixel quad (VEC) or per pixel, all of its
-// channels; the sample index is one scalar division per block and t / wt / gper / w are scalar loads.  Nothing passed by
-// value changes from step to step: the upstream gradient and the guidance weight are read from device memory.
-template <bool VEC>
-__global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restrict__ out, const float* __restrict__ teach,
-                                                          int cfg_mode, const float* __restrict__ w_dev,
-                                                          const int64_t* __restrict__ t, const float* __restrict__ wt,
-                                                          const float* __restrict__ gper, float gscale, int kind, int b, int c,
-                                                          int hw, unsigned bps, float* __restrict__ gout) {
+// element-wise over [b, c, hw]: `bps` blocks per sample, a thread per pixel quad (W == 4) or per pixel, all of its channels; the
+// sample index is one scalar division per block and t / wt / gper / w are scalar loads.  Nothing passed by value changes from
+// step to step: the upstream gradient and the guidance weight are read from device memory.
+template <int W>
+__global__ __launch_bounds__(LOSS_BWD_THREADS) void distill_bwd_kernel(const float* __restrict__ out, const float* __restrict__ teach,
+                                                                       int cfg_mode, const float* __restrict__ w_dev,
+                                                                       const int64_t* __restrict__ t, const float* __restrict__ wt,
+                                                                       const float* __restrict__ gper, float gscale, int kind,
+                                                                       int b, int c, int hw, unsigned bps,
+                                                                       float* __restrict__ gout) {
     const int n = blockIdx.x / bps;
-    const long u = (long)(blockIdx.x % bps) * 256 + threadIdx.x;            // pixel quad (VEC) or pixel of the sample
-    if (u >= (VEC ? hw / 4 : hw)) return;
+    const long u = (long)(blockIdx.x % bps) * LOSS_BWD_THREADS + threadIdx.x;
+    if (u >= hw / W) return;
     const float w = cfg_mode ? *w_dev : 0.f;
     float k = (gper[n] * (wt ? wt[t[n]] : 1.f)) / (float)((long)c * hw);
     k = k * gscale;
-    const long base = (long)n * c * hw;
-    if (VEC) {
-        const int p = 4 * (int)u;
-        for (int cc = 0; cc < c; ++cc) {
-            const long i = base + (long)cc * hw + p;
-            const f32x4 o = *reinterpret_cast<const f32x4*>(out + i);
-            f32x4 g;
+    const int p = W * (int)u;
+    for (int cc = 0; cc < c; ++cc) {
+        const long i = ((long)n * c + cc) * hw + p;
+        const loss_vec<W> o = loss_load<W>(out, i);
+        loss_vec<W> g;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) g[j] = distill_grad(kind, o[j] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p + j), k);
-            *reinterpret_cast<f32x4*>(gout + i) = g;
-        }
-    } else {
-        const int p = (int)u;
-        for (int cc = 0; cc < c; ++cc) {
-            const long i = base + (long)cc * hw + p;
-            gout[i] = distill_grad(kind, out[i] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p), k);
-        }
+        for (int j = 0; j < W; ++j) g[j] = loss_grad(kind, o[j] - guided(teach, cfg_mode, w, b, n, c, hw, cc, p + j), k);
+        loss_store<W>(gout, i, g);
     }
 }
 
@@ -124,7 +89,9 @@ bool distill_args_ok(const float* out, const float* teach, int32_t cfg_mode, con
     return (long)c * hw <= INT32_MAX && 2L * b <= INT32_MAX;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the 16-byte path: a whole number of pixel quads per plane, `out` and `gout` on a 16-byte boundary (the teacher is read float by
+// float and may sit anywhere)
+bool distill_vec_ok(const float* out, int32_t hw, const float* gout) { return hw % 4 == 0 && aligned16(out) && aligned16(gout); }
 
 }  // namespace
 
@@ -133,13 +100,8 @@ extern "C" int sgd_distill_loss_fwd(const float* out, const float* teach, int32_
                                     void* stream) {
     SGD_CLEAR_ERR();
     if (!distill_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !per_raw || !per_w) return SGD_ERR_ARG;
-    if (hw % 4 == 0 && aligned16(out))
-        hipLaunchKernelGGL(distill_fwd_kernel<true>, dim3(b), dim3(DISTILL_THREADS), 0, (hipStream_t)stream, out, teach, cfg_mode,
-                           w_dev, t, wt, kind, b, c, hw, per_raw, per_w);
-    else
-        hipLaunchKernelGGL(distill_fwd_kernel<false>, dim3(b), dim3(DISTILL_THREADS), 0, (hipStream_t)stream, out, teach, cfg_mode,
-                           w_dev, t, wt, kind, b, c, hw, per_raw, per_w);
-    return sgd_check_launch();
+    return loss_launch(distill_vec_ok(out, hw, nullptr), distill_fwd_kernel<4>, distill_fwd_kernel<1>, (unsigned)b,
+                       LOSS_FWD_THREADS, stream, out, teach, cfg_mode, w_dev, t, wt, kind, b, c, hw, per_raw, per_w);
 }
 
 extern "C" int sgd_distill_loss_bwd(const float* out, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* t,
@@ -147,16 +109,9 @@ extern "C" int sgd_distill_loss_bwd(const float* out, const float* teach, int32_
                                     float gscale, float* gout, void* stream) {
     SGD_CLEAR_ERR();
     if (!distill_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !gper || !gout) return SGD_ERR_ARG;
-    const bool vec = hw % 4 == 0 && aligned16(out) && aligned16(gout);
-    const int64_t units = vec ? hw / 4 : hw;
-    const int64_t bps = (units + 255) / 256;
-    if (bps > INT32_MAX / b) return SGD_ERR_ARG;
-    const dim3 grid((unsigned)(bps * b));
-    if (vec)
-        hipLaunchKernelGGL(distill_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, teach, cfg_mode, w_dev, t, wt,
-                           gper, gscale, kind, b, c, hw, (unsigned)bps, gout);
-    else
-        hipLaunchKernelGGL(distill_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, teach, cfg_mode, w_dev, t, wt,
-                           gper, gscale, kind, b, c, hw, (unsigned)bps, gout);
-    return sgd_check_launch();
+    const bool vec = distill_vec_ok(out, hw, gout);
+    const unsigned bps = loss_bps(vec, hw, b);
+    if (!bps) return SGD_ERR_ARG;
+    return loss_launch(vec, distill_bwd_kernel<4>, distill_bwd_kernel<1>, bps * b, LOSS_BWD_THREADS, stream, out, teach, cfg_mode,
+                       w_dev, t, wt, gper, gscale, kind, b, c, hw, bps, gout);
 }

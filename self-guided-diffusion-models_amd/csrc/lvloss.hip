@@ -2,7 +2,7 @@
 // (gfx950; include/sgdm_hip.h: sgd_lv_loss_fwd, sgd_lv_loss_bwd; the reference has no learned variance).  `out` is the model
 // output [b, 2C, hw] in NCHW: m = out[:, :C] predicts the trained target, v = out[:, C:] interpolates the reverse-process
 // log-variance between max_log[t] = log beta_t and min_log[t] = log beta~_t.  Per element, t = t[n]:
-//   simple  l  = loss_elem(m - target)                          exactly sgd_loss_fwd's term (csrc/loss.hip) on the mean half
+//   simple  l  = loss_elem(m - target)                          sgd_loss_fwd's term on the mean half (csrc/loss_common.h)
 //   x_t     = sa x0 + s1 noise                                  (the bits of sgd_q_sample)
 //   x0p     = r0 x_t - r1 m (par 0) | m (par 1) | sa x_t - s1 m (par 2),    not clipped
 //   mu_th   = c1 x0p + c2 x_t,   mu_q = c1 x0 + c2 x_t
@@ -15,15 +15,14 @@
 // deviations out.  t is per sample, so the branch is uniform per workgroup (forward) and per block (backward).
 //
 // This file is compiled with -ffp-contract=off (build.py: FILE_FLAGS), like loss.hip: the simple term and the mean-half
-// gradient carry the bits of sgd_loss_fwd / sgd_loss_bwd.  The gradient of L stops at the mean (the paper's rule): the mean
-// half gets sgd_loss_bwd's gradient, the variance half gper_vlb / (C hw) * dL/dlv * 0.5 (max_log - min_log).
-#include "sgdm_common.h"
+// gradient are loss_elem / loss_grad / loss_target of csrc/loss_common.h, the code of sgd_loss_fwd / sgd_loss_bwd.  The gradient
+// of L stops at the mean (the paper's rule): the mean half gets sgd_loss_bwd's gradient, the variance half
+// gper_vlb / (C hw) * dL/dlv * 0.5 (max_log - min_log).
+#include "loss_common.h"
 #include "../../include/sgdm_hip.h"
 
 namespace {
 
-constexpr int LV_THREADS = 1024;                    // forward: one workgroup per sample, 16 waves
-constexpr int LV_WAVES = LV_THREADS / 64;
 constexpr float LV_LN2 = 0.6931471805599453f;
 constexpr double LV_LN2_D = 0.6931471805599453;
 constexpr double LV_SQRT_2_PI = 0.7978845608028654;  // sqrt(2 / pi)
@@ -38,25 +37,6 @@ __device__ __forceinline__ lv_coef lv_load(const lv_tables& tb, int64_t tt, int 
     lv_coef c = {tb.sa[tt], tb.s1[tt], 0.f, 0.f, tb.c1[tt], tb.c2[tt], tb.mx[tt], tb.mn[tt]};
     if (par == 0) { c.r0 = tb.r0[tt]; c.r1 = tb.r1[tt]; }
     return c;
-}
-
-__device__ __forceinline__ float lv_target(int par, float xi, float ni, const lv_coef& c) {
-    if (par == 0) return ni;
-    if (par == 1) return xi;
-    return c.sa * ni - c.s1 * xi;                   // two rounded products, as loss_target (csrc/loss.hip)
-}
-
-__device__ __forceinline__ float lv_elem(int kind, float d) {
-    if (kind == 0) return d * d;
-    const float ad = fabsf(d);
-    if (kind == 1) return ad;
-    return ad < 1.f ? 0.5f * d * d : ad - 0.5f;
-}
-
-__device__ __forceinline__ float lv_grad(int kind, float d, float k) {
-    if (kind == 0) return (2.f * k) * d;
-    if (kind == 1) return k * (d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f);
-    return k * fminf(fmaxf(d, -1.f), 1.f);
 }
 
 // t > 0, fp32: the KL of the two Gaussians in bits (dl == nullptr) and, for the backward, dL / dlv
@@ -102,54 +82,36 @@ __device__ __forceinline__ double lv_decoder(int par, float m, float v, float xi
     return -log(fmax(P, 1e-12)) / LV_LN2_D;
 }
 
-__device__ __forceinline__ double lv_block_sum(double acc, double* red) {
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < LV_WAVES; ++i) s += red[i];
-    return s;
-}
-
-// VEC: hw % 4 == 0 and every tensor 16-byte aligned (then both halves of every sample start on a 16-byte boundary): consecutive
-// lanes read consecutive 16-byte quads of m, v, x0 and noise.  Otherwise one float per lane.  Sums as sgd_loss_fwd: per-thread
-// partials in double, xor-shuffles inside each wave, one LDS slot per wave folded in ascending order by thread 0; no atomics.
-template <bool VEC>
-__global__ __launch_bounds__(LV_THREADS) void lv_loss_fwd_kernel(const float* __restrict__ out, const float* __restrict__ x0,
-                                                                 const float* __restrict__ noise, const int64_t* __restrict__ t,
-                                                                 lv_tables tb, const float* __restrict__ wt, int par, int kind,
-                                                                 long chw, float* __restrict__ per_raw, float* __restrict__ per_w,
-                                                                 float* __restrict__ per_vlb) {
-    __shared__ double red_s[LV_WAVES], red_v[LV_WAVES];
+// W == 4: hw % 4 == 0 and every tensor 16-byte aligned (then both halves of every sample start on a 16-byte boundary):
+// consecutive lanes read consecutive 16-byte quads of m, v, x0 and noise.  W == 1: one float per lane.  Two sums, each as
+// loss_block_sum (csrc/loss_common.h).
+template <int W>
+__global__ __launch_bounds__(LOSS_FWD_THREADS) void lv_loss_fwd_kernel(const float* __restrict__ out, const float* __restrict__ x0,
+                                                                       const float* __restrict__ noise,
+                                                                       const int64_t* __restrict__ t, lv_tables tb,
+                                                                       const float* __restrict__ wt, int par, int kind, long chw,
+                                                                       float* __restrict__ per_raw, float* __restrict__ per_w,
+                                                                       float* __restrict__ per_vlb) {
+    __shared__ double red_s[LOSS_FWD_THREADS / 64], red_v[LOSS_FWD_THREADS / 64];
     const int n = blockIdx.x;
     const int64_t tt = t[n];
     const lv_coef c = lv_load(tb, tt, par);
     const float* __restrict__ mp = out + 2 * (long)n * chw;
-    const float* __restrict__ vp = mp + chw;
     const long base = (long)n * chw;
     const bool dec = tt == 0;
     double acc_s = 0.0, acc_v = 0.0;
-    if (VEC) {
-        for (long q = threadIdx.x; q < chw / 4; q += LV_THREADS) {
-            const f32x4 mv = *reinterpret_cast<const f32x4*>(mp + 4 * q), vv = *reinterpret_cast<const f32x4*>(vp + 4 * q);
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + base + 4 * q);
-            const f32x4 nv = *reinterpret_cast<const f32x4*>(noise + base + 4 * q);
+    for (long u = threadIdx.x; u < chw / W; u += LOSS_FWD_THREADS) {
+        const long e = W * u;
+        const loss_vec<W> mv = loss_load<W>(mp, e), vv = loss_load<W>(mp, chw + e);
+        const loss_vec<W> xv = loss_load<W>(x0, base + e), nv = loss_load<W>(noise, base + e);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc_s += (double)lv_elem(kind, mv[j] - lv_target(par, xv[j], nv[j], c));
-                acc_v += dec ? lv_decoder(par, mv[j], vv[j], xv[j], nv[j], c, nullptr)
-                             : (double)lv_kl(par, mv[j], vv[j], xv[j], nv[j], c, nullptr);
-            }
-        }
-    } else {
-        for (long e = threadIdx.x; e < chw; e += LV_THREADS) {
-            const float m = mp[e], v = vp[e], xi = x0[base + e], ni = noise[base + e];
-            acc_s += (double)lv_elem(kind, m - lv_target(par, xi, ni, c));
-            acc_v += dec ? lv_decoder(par, m, v, xi, ni, c, nullptr) : (double)lv_kl(par, m, v, xi, ni, c, nullptr);
+        for (int j = 0; j < W; ++j) {
+            acc_s += (double)loss_elem(kind, mv[j] - loss_target(par, xv[j], nv[j], c.sa, c.s1));
+            acc_v += dec ? lv_decoder(par, mv[j], vv[j], xv[j], nv[j], c, nullptr)
+                         : (double)lv_kl(par, mv[j], vv[j], xv[j], nv[j], c, nullptr);
         }
     }
-    const double ss = lv_block_sum(acc_s, red_s), sv = lv_block_sum(acc_v, red_v);
+    const double ss = loss_block_sum<LOSS_FWD_THREADS>(acc_s, red_s), sv = loss_block_sum<LOSS_FWD_THREADS>(acc_v, red_v);
     if (threadIdx.x == 0) {
         const float raw = (float)(ss / (double)chw);
         per_raw[n] = raw;
@@ -158,59 +120,44 @@ __global__ __launch_bounds__(LV_THREADS) void lv_loss_fwd_kernel(const float* __
     }
 }
 
-// `bps` blocks of 256 threads per sample, a thread per quad (VEC) or per element of [C, hw]: it writes the element's gradient in
-// BOTH halves, so every input is read once.  gper_w / gper_vlb are read from device memory: nothing by value depends on the step.
-template <bool VEC>
-__global__ __launch_bounds__(256) void lv_loss_bwd_kernel(const float* __restrict__ out, const float* __restrict__ x0,
-                                                          const float* __restrict__ noise, const int64_t* __restrict__ t,
-                                                          lv_tables tb, const float* __restrict__ wt,
-                                                          const float* __restrict__ gper_w, const float* __restrict__ gper_vlb,
-                                                          int par, int kind, long chw, unsigned bps, float* __restrict__ gout) {
+// `bps` blocks per sample, a thread per quad (W == 4) or per element of [C, hw]: it writes the element's gradient in BOTH halves,
+// so every input is read once.  gper_w / gper_vlb are read from device memory: nothing by value depends on the step.
+template <int W>
+__global__ __launch_bounds__(LOSS_BWD_THREADS) void lv_loss_bwd_kernel(const float* __restrict__ out, const float* __restrict__ x0,
+                                                                       const float* __restrict__ noise,
+                                                                       const int64_t* __restrict__ t, lv_tables tb,
+                                                                       const float* __restrict__ wt,
+                                                                       const float* __restrict__ gper_w,
+                                                                       const float* __restrict__ gper_vlb, int par, int kind,
+                                                                       long chw, unsigned bps, float* __restrict__ gout) {
     const int n = blockIdx.x / bps;
-    const long u = (long)(blockIdx.x % bps) * 256 + threadIdx.x;
-    if (u >= (VEC ? chw / 4 : chw)) return;
+    const long u = (long)(blockIdx.x % bps) * LOSS_BWD_THREADS + threadIdx.x;
+    if (u >= chw / W) return;
     const int64_t tt = t[n];
     const lv_coef c = lv_load(tb, tt, par);
     const float k = (gper_w[n] * (wt ? wt[tt] : 1.f)) / (float)chw;           // sgd_loss_bwd's factor (its gscale is 1)
     const float kv = (gper_vlb[n] / (float)chw) * (0.5f * (c.mx - c.mn));
     const double kvd = ((double)gper_vlb[n] / (double)chw) * (0.5 * ((double)c.mx - (double)c.mn));
     const bool dec = tt == 0;
-    const long e0 = VEC ? 4 * u : u;
-    const float* __restrict__ mp = out + 2 * (long)n * chw + e0;
-    float* __restrict__ gm = gout + 2 * (long)n * chw + e0;
-    const long i = (long)n * chw + e0;
-    if (VEC) {
-        const f32x4 mv = *reinterpret_cast<const f32x4*>(mp), vv = *reinterpret_cast<const f32x4*>(mp + chw);
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + i), nv = *reinterpret_cast<const f32x4*>(noise + i);
-        f32x4 g, gv;
+    const long e = 2 * (long)n * chw + W * u, i = (long)n * chw + W * u;      // in out / gout (mean half), in x0 / noise
+    const loss_vec<W> mv = loss_load<W>(out, e), vv = loss_load<W>(out, e + chw);
+    const loss_vec<W> xv = loss_load<W>(x0, i), nv = loss_load<W>(noise, i);
+    loss_vec<W> g, gv;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            g[j] = lv_grad(kind, mv[j] - lv_target(par, xv[j], nv[j], c), k);
-            if (dec) {
-                double dl;
-                lv_decoder(par, mv[j], vv[j], xv[j], nv[j], c, &dl);
-                gv[j] = (float)(kvd * dl);
-            } else {
-                float dl;
-                lv_kl(par, mv[j], vv[j], xv[j], nv[j], c, &dl);
-                gv[j] = kv * dl;
-            }
-        }
-        *reinterpret_cast<f32x4*>(gm) = g;
-        *reinterpret_cast<f32x4*>(gm + chw) = gv;
-    } else {
-        const float m = mp[0], v = mp[chw], xi = x0[i], ni = noise[i];
-        gm[0] = lv_grad(kind, m - lv_target(par, xi, ni, c), k);
+    for (int j = 0; j < W; ++j) {
+        g[j] = loss_grad(kind, mv[j] - loss_target(par, xv[j], nv[j], c.sa, c.s1), k);
         if (dec) {
             double dl;
-            lv_decoder(par, m, v, xi, ni, c, &dl);
-            gm[chw] = (float)(kvd * dl);
+            lv_decoder(par, mv[j], vv[j], xv[j], nv[j], c, &dl);
+            gv[j] = (float)(kvd * dl);
         } else {
             float dl;
-            lv_kl(par, m, v, xi, ni, c, &dl);
-            gm[chw] = kv * dl;
+            lv_kl(par, mv[j], vv[j], xv[j], nv[j], c, &dl);
+            gv[j] = kv * dl;
         }
     }
+    loss_store<W>(gout, e, g);
+    loss_store<W>(gout, e + chw, gv);
 }
 
 bool lv_args_ok(const float* out, const float* x0, const float* noise, const int64_t* t, const sgd_lv_tables* tb, int32_t par,
@@ -222,10 +169,8 @@ bool lv_args_ok(const float* out, const float* x0, const float* noise, const int
     return (int64_t)c * hw <= INT64_MAX / 2 / b;
 }
 
-bool lv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 bool lv_vec_ok(const float* out, const float* x0, const float* noise, int32_t hw, const float* gout) {
-    return hw % 4 == 0 && lv_aligned16(out) && lv_aligned16(x0) && lv_aligned16(noise) && lv_aligned16(gout);
+    return hw % 4 == 0 && aligned16(out) && aligned16(x0) && aligned16(noise) && aligned16(gout);
 }
 
 lv_tables lv_dev_tables(const sgd_lv_tables* tb) {
@@ -241,14 +186,9 @@ extern "C" int sgd_lv_loss_fwd(const float* out, const float* x0, const float* n
     SGD_CLEAR_ERR();
     if (!lv_args_ok(out, x0, noise, t, tables, par, kind, b, c, hw) || !per_raw || !per_w || !per_vlb) return SGD_ERR_ARG;
     const long chw = (long)c * hw;
-    const lv_tables tb = lv_dev_tables(tables);
-    if (lv_vec_ok(out, x0, noise, hw, nullptr))
-        hipLaunchKernelGGL(lv_loss_fwd_kernel<true>, dim3(b), dim3(LV_THREADS), 0, (hipStream_t)stream, out, x0, noise, t, tb, wt,
-                           par, kind, chw, per_raw, per_w, per_vlb);
-    else
-        hipLaunchKernelGGL(lv_loss_fwd_kernel<false>, dim3(b), dim3(LV_THREADS), 0, (hipStream_t)stream, out, x0, noise, t, tb, wt,
-                           par, kind, chw, per_raw, per_w, per_vlb);
-    return sgd_check_launch();
+    return loss_launch(lv_vec_ok(out, x0, noise, hw, nullptr), lv_loss_fwd_kernel<4>, lv_loss_fwd_kernel<1>, (unsigned)b,
+                       LOSS_FWD_THREADS, stream, out, x0, noise, t, lv_dev_tables(tables), wt, par, kind, chw, per_raw, per_w,
+                       per_vlb);
 }
 
 extern "C" int sgd_lv_loss_bwd(const float* out, const float* x0, const float* noise, const int64_t* t, const sgd_lv_tables* tables,
@@ -258,16 +198,8 @@ extern "C" int sgd_lv_loss_bwd(const float* out, const float* x0, const float* n
     if (!lv_args_ok(out, x0, noise, t, tables, par, kind, b, c, hw) || !gper_w || !gper_vlb || !gout) return SGD_ERR_ARG;
     const long chw = (long)c * hw;
     const bool vec = lv_vec_ok(out, x0, noise, hw, gout);
-    const int64_t units = vec ? chw / 4 : chw;
-    const int64_t bps = (units + 255) / 256;
-    if (bps > INT32_MAX / b) return SGD_ERR_ARG;
-    const lv_tables tb = lv_dev_tables(tables);
-    const dim3 grid((unsigned)(bps * b));
-    if (vec)
-        hipLaunchKernelGGL(lv_loss_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, out, x0, noise, t, tb, wt, gper_w,
-                           gper_vlb, par, kind, chw, (unsigned)bps, gout);
-    else
-        hipLaunchKernelGGL(lv_loss_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, x0, noise, t, tb, wt, gper_w,
-                           gper_vlb, par, kind, chw, (unsigned)bps, gout);
-    return sgd_check_launch();
+    const unsigned bps = loss_bps(vec, chw, b);
+    if (!bps) return SGD_ERR_ARG;
+    return loss_launch(vec, lv_loss_bwd_kernel<4>, lv_loss_bwd_kernel<1>, bps * b, LOSS_BWD_THREADS, stream, out, x0, noise, t,
+                       lv_dev_tables(tables), wt, gper_w, gper_vlb, par, kind, chw, bps, gout);
 }

@@ -21,15 +21,15 @@ and update from x0 = sa x - s1 v, eps = sa v + s1 x in ONE launch that never div
 and what ``p_sample_loop`` chooses for a model with the hparam.
 Also without a counterpart, on the training side: the hparam ``loss_weighting`` ('min_snr', Hang et al. 2023; 'trunc_snr',
 Salimans & Ho 2022; 'p2', Choi et al. 2022; 'table'): ``loss_weight_table`` builds the per-timestep weights on the loss of the
-trained target, ``Schedule_DDPM`` keeps them as the buffer ``loss_weights`` and ``train.p_losses_hip`` applies them inside the
+trained target, ``Schedule_DDPM`` keeps them as the buffer ``loss_weights`` and ``losses.p_losses_hip`` applies them inside the
 loss kernels (include/sgdm_hip.h: sgd_loss_fwd / sgd_loss_bwd).
 Also without a counterpart, learned variance (Nichol & Dhariwal 2021): the hparams ``learn_sigma`` / ``vlb_weight`` (the UNet is
-2C channels wide; buffers ``lv_max_log`` / ``lv_min_log``; ``train.p_losses_hip`` adds the variational bound through
+2C channels wide; buffers ``lv_max_log`` / ``lv_min_log``; ``losses.p_losses_hip`` adds the variational bound through
 sgd_lv_loss_fwd / sgd_lv_loss_bwd), the 'native' update ``_LVUpdate`` (sgd_ddpm_lv_step) that samples with it, the sampling kwarg
 ``native_steps`` = K (``native_times``, ``native_rows``: a strided ancestral chain, fixed or learned variance), the C-row head of
 every other sampler (``_StepRunner.head``) and ``LatentDiffusion.calc_bpd``.
 Also without a counterpart, guidance distillation (Meng et al. 2023, stage 1): the hparams ``distill_guidance`` = w /
-``distill_rescale`` = phi (``distill_option``) and ``LatentDiffusion.set_distill_teacher`` make ``train.p_losses_hip`` train the
+``distill_rescale`` = phi (``distill_option``) and ``LatentDiffusion.set_distill_teacher`` make ``losses.p_losses_hip`` train the
 conditional evaluation against the teacher's guided output (include/sgdm_hip.h: sgd_distill_loss_fwd / sgd_distill_loss_bwd); the
 sampling kwarg ``cfg_distilled`` (hparam ``guidance_distilled``) samples such a student with ONE evaluation at B per step, on the
 captured step the batch-B graph alone (``_GraphedStep``: no 2B engine is built).
@@ -991,11 +991,11 @@ class Schedule_DDPM(nn.Module):
         if self.zero_terminal_snr and h.parameterization == "eps":
             raise ValueError("zero_terminal_snr with parameterization='eps': at SNR 0 the input is the noise, so the target "
                              "carries no information; use 'v' (or 'x0')")
-        # optional hparams (not in the reference): per-timestep loss weights, buffer ``loss_weights`` (sgdm_amd/train.py)
+        # optional hparams (not in the reference): per-timestep loss weights, buffer ``loss_weights`` (sgdm_amd/losses.py)
         self.loss_weighting = loss_weighting_option(h)
         # optional hparams (not in the reference; Nichol & Dhariwal 2021): the network is 2C channels wide and the second half
         # of its output interpolates the reverse-process log-variance between the buffers lv_min_log and lv_max_log; the loss
-        # is L_simple + vlb_weight * L_vlb (sgdm_amd/train.py).  The UNet's width is checked where it is attached
+        # is L_simple + vlb_weight * L_vlb (sgdm_amd/losses.py).  The UNet's width is checked where it is attached
         # (LatentDiffusion.set_denoise_fn) and on every output (p_losses).
         self.learn_sigma = bool(getattr(h, "learn_sigma", False))
         self.vlb_weight = None
@@ -1579,7 +1579,7 @@ class LatentDiffusion(nn.Module):
         self.sampler = Schedule_DDPM(**kwargs)
         h = self.hparams
         # optional hparams (not in the reference; Meng et al. 2023, stage 1): the training target is the guided output of a
-        # frozen teacher (set_distill_teacher; sgdm_amd/train.py)
+        # frozen teacher (set_distill_teacher; sgdm_amd/losses.py)
         self.distill = distill_option(h)
         self.sampler_list = {
             "native": self.sampler,
@@ -1620,7 +1620,7 @@ class LatentDiffusion(nn.Module):
         return self.p_losses(x, t, *args, **kwargs)
 
     def p_losses(self, x_start, t, noise=None, *args, **kwargs):
-        from .train import p_losses_hip
+        from .losses import p_losses_hip
         return p_losses_hip(self, x_start, t, noise, *args, **kwargs)
 
     @torch.no_grad()
@@ -1634,7 +1634,7 @@ class LatentDiffusion(nn.Module):
         if not s.learn_sigma:
             raise ValueError("calc_bpd needs a learned-variance model (hparam learn_sigma): a fixed-variance model has no "
                              "variational bound to report")
-        from .train import lv_terms
+        from .losses import lv_terms
         T, B = self.hparams.num_timesteps, x_start.shape[0]
         x_start = x_start.float()
         vb = torch.empty(B, T, dtype=torch.float32, device=x_start.device)

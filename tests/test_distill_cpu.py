@@ -313,6 +313,23 @@ def test_the_hparam_guidance_distilled_sets_the_kwarg(monkeypatch):
         assert seen.get("cfg_distilled") is want, (hp, given)
 
 
+# --------------------------------------------------------------------------------------------------------------- loss path
+
+def test_loss_path_of_every_combination():
+    """the one decision p_losses_hip takes: a distillation step never runs the weighted kernels (they form the trained
+    target, not the teacher's); without a drop-in UNet teacher on the device it is the torch chain on the teacher's tensor"""
+    from sgdm_amd.losses import _loss_path
+    unet, w = object(), object()
+    for lv, distilling, d_unet, weights, on_dev, want in (
+            (False, False, None, None, True, "torch"), (False, False, None, None, False, "torch"),
+            (False, False, None, w, True, "weighted_fused"), (False, False, None, w, False, "torch"),
+            (False, True, unet, None, True, "distill_fused"), (False, True, unet, w, True, "distill_fused"),
+            (False, True, None, None, True, "torch"), (False, True, None, w, True, "torch"),
+            (False, True, None, None, False, "torch"), (False, True, None, w, False, "torch"),
+            (True, False, None, None, True, "lv"), (True, False, None, w, True, "lv"), (True, False, None, w, False, "lv")):
+        assert _loss_path(lv, distilling, d_unet, weights, on_dev) == want, (lv, distilling, d_unet, weights, on_dev)
+
+
 # ----------------------------------------------------------------------------------------------------------------- binding
 
 def test_binding_declares_both_entries_and_the_abi_stays():

@@ -117,8 +117,10 @@ def _rel(got, want):
 
 
 # (b, c, hw, offset in floats): the 16-byte path on several waves; an odd chw on the scalar path from buffers 4 bytes past a
-# 16-byte boundary; one sample of one wave
-SHAPES = [(3, 3, 256, 0), (2, 3, 25, 1), (1, 4, 64, 0)]
+# 16-byte boundary; one sample of one wave; 1026 quads per plane: the forward workgroup (1024 threads) strides its loop a second
+# time, the backward takes 5 blocks per sample, the last with 2 live threads; the same past 1024 threads on the scalar path with
+# an odd hw; hw % 4 == 0 but 4 bytes off a 16-byte boundary, which must take the scalar path
+SHAPES = [(3, 3, 256, 0), (2, 3, 25, 1), (1, 4, 64, 0), (2, 3, 4104, 0), (2, 3, 1029, 1), (1, 4, 64, 1)]
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
@@ -305,7 +307,7 @@ def _explicit_target(teacher, x, t, ukw, phi):
 def test_training_step_against_the_explicit_target(par, prec, phi, pairs, monkeypatch):
     """one distillation p_losses + backward on the c32 model against the same student step with the explicit target fed to
     _MSEFn; the launches counted: one loss kernel each way, no combine, no re-layout of the teacher's output"""
-    from sgdm_amd.train import _MSEFn
+    from sgdm_amd.losses import _MSEFn
     m, teacher, x0, noise, ukw = pairs(prec)
     hp = dict(distill_rescale=phi) if phi else {}
     d = _diffusion(parameterization=par, distill_guidance=W, **hp).train()
@@ -370,6 +372,45 @@ def test_loss_weighting_applies_and_validation_launches_the_forward_kernel_only(
     assert sorted(vd) == ["val/ddpm_loss", "val/ddpm_loss_raw", "val/loss"] and not vloss.requires_grad
     # (the student's inference forward is not its training forward bit for bit: the 1e-4 parity contract)
     assert float(vloss) == pytest.approx(float(loss), rel=1e-3)
+
+
+@pytest.mark.parametrize("loss_type", ["l2", "huber"])
+def test_callable_teacher_with_loss_weighting_trains_against_the_teacher(loss_type, pairs, monkeypatch):
+    """a teacher that is not a drop-in UNet (a plain callable) on the device, loss_weighting on: the torch chain on the teacher's
+    guided output times the weights -- NOT the weighted kernels, which form the trained target (here v) themselves.  Bound: the
+    1e-6 relative of the weighted step above (an fp32 mean of 768 terms against float64)."""
+    m, teacher, x0, noise, ukw = pairs("f32")
+    d = _diffusion(parameterization="v", loss_type=loss_type, loss_weighting="min_snr", distill_guidance=W).train()
+    seen = _attach(d, m)
+    asked = []
+
+    def teach(x, t, w, cond=None, **kw):
+        asked.append(w)
+        return teacher.forward_with_cond_scale(x, t, w, cond=cond, **kw)
+    d.set_distill_teacher(teach)
+    t = torch.tensor([3, 999, 250, 731]).cuda()
+    calls = _count(monkeypatch, *ENTRIES)
+    loss, ld, first, _ = _step(d, m, x0, t, noise, ukw)
+    assert asked == [W]
+    assert calls["sgd_loss_fwd"] == 0 and calls["sgd_loss_bwd"] == 0
+    assert calls["sgd_distill_loss_fwd"] == 0 and calls["sgd_distill_loss_bwd"] == 0
+    assert calls["sgd_q_sample"] == 1 and calls["sgd_q_sample_v"] == 0
+    diff = seen["out"].double() - _explicit_target(teacher, seen["x_noisy"], t, ukw, 0.0).double()
+    el = diff ** 2 if loss_type == "l2" else torch.where(diff.abs() < 1, 0.5 * diff ** 2, diff.abs() - 0.5)
+    per = el.reshape(N, -1).mean(1)
+    want = (d.sampler.loss_weights[t].double() * per).mean()
+    err = abs(float(loss) - float(want)) / float(want)
+    err_y = max_rel(ld["train/epoch_stats_y"].cpu(), per.cpu())
+    # the trained target would give another loss altogether
+    sa, s1 = (v[t].view(N, 1, 1, 1).double() for v in (d.sampler.sqrt_alphas_cumprod, d.sampler.sqrt_one_minus_alphas_cumprod))
+    dv = seen["out"].double() - (sa * noise.double() - s1 * x0.double())
+    elv = dv ** 2 if loss_type == "l2" else torch.where(dv.abs() < 1, 0.5 * dv ** 2, dv.abs() - 0.5)
+    other = (d.sampler.loss_weights[t].double() * elv.reshape(N, -1).mean(1)).mean()
+    print(f"weighted {loss_type} distillation step, callable teacher: loss rel err {err:.2e}, unweighted per-sample {err_y:.2e}; "
+          f"against the v target it would be {float(other):.4e}, not {float(want):.4e}")
+    assert sorted(ld) == ["train/ddpm_loss", "train/ddpm_loss_raw", "train/epoch_stats_x", "train/epoch_stats_y", "train/loss"]
+    assert err <= 1e-6 and err_y <= 1e-6 and float(first.abs().max()) > 0
+    assert abs(float(other) - float(want)) > 1e-3 * float(want)
 
 
 def test_refusals_come_before_any_launch(pairs, monkeypatch):

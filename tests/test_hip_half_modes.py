@@ -405,7 +405,7 @@ def test_teacher_forced_guided_evaluations(name, mode):
 # ===================================================================================================================== D
 @pytest.mark.parametrize("mode", MODES)
 def test_training_refuses_the_mode_before_any_launch(mode):
-    from sgdm_amd.train import p_losses_hip
+    from sgdm_amd.losses import p_losses_hip
     m, entry = build_model("uf_label_c32_s16", mode)
     m.train()
     v, x, t, cond, layout = inputs("uf_label_c32_s16")

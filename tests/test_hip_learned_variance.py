@@ -163,7 +163,7 @@ def _restate(c, tb, par, kind, weighted, gw, gv, dtype):
 
 def _launch(lib, s, c, par, kind, weighted, gw, gv, offset):
     from sgdm_amd import _lib as L
-    from sgdm_amd.train import _lv_tables
+    from sgdm_amd.losses import _lv_tables
     from sgdm_amd.unet import _ptr
     import ctypes as C
     b, Cc, hw = c["x0"].shape
@@ -262,7 +262,7 @@ def test_loss_kernels(b, Cc, hw, offset, sched, scheds):
 def test_loss_entries_refuse_bad_arguments(scheds):
     import ctypes as C
     from sgdm_amd import _lib as L
-    from sgdm_amd.train import _lv_tables
+    from sgdm_amd.losses import _lv_tables
     from sgdm_amd.unet import _ptr
     lib = L.load()
     s = scheds["plain"]
@@ -451,7 +451,7 @@ def _loss64(d, par, kind, x0, noise, x_noisy, out, t, weights):
 @pytest.mark.parametrize("prec", ["f32", "f16x3"])
 @pytest.mark.parametrize("par,extra", [("eps", {}), ("v", dict(loss_weighting="min_snr"))])
 def test_training_step_with_learned_variance(par, extra, prec, wide, monkeypatch):
-    from sgdm_amd.train import _simple_torch, lv_vlb_torch
+    from sgdm_amd.losses import lv_vlb_torch, simple_loss_torch as _simple_torch
     m, sd, batch = wide
     m.train()
     m.hip_precision = prec

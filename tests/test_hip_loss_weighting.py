@@ -286,7 +286,7 @@ def _per64(d, par, loss_type, x0, noise, out, t):
 def test_training_step_with_weights(par, scheme, trainer, monkeypatch):
     """one weighted p_losses + backward on the c32 model: the loss against the float64 restatement on the observed x_noisy
     and model output, the gradients against the same step through the existing l2 path times the weights"""
-    from sgdm_amd.train import _MSEFn
+    from sgdm_amd.losses import _MSEFn
     m, x0, noise, ukw = trainer
     d = _diffusion(parameterization=par, loss_weighting=scheme).train()
     seen = _attach(d, m)

@@ -294,7 +294,7 @@ def test_training_step_with_v_target():
     """one p_losses + backward on the c32 model: the loss against the torch restatement on the same x_noisy and model
     output, the gradients against the same step run with the restated target through the existing l2 path (_MSEFn)"""
     from sgdm_amd.synth import synth_batch
-    from sgdm_amd.train import _MSEFn
+    from sgdm_amd.losses import _MSEFn
     m, entry = build_model("uf_clusterlayout_c32_s16", "f32")
     m.train()
     d = _diffusion("v").train()

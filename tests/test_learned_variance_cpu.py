@@ -228,7 +228,7 @@ def _restate(s, out, x0, noise, t, par, kind, wt=None):
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("par", PARS)
 def test_cpu_branch_against_float64_restatement(par, kind, decoder):
-    from sgdm_amd.train import lv_loss
+    from sgdm_amd.losses import lv_loss
     d = _diffusion(learn_sigma=True, parameterization=par, loss_type=kind, loss_weighting="min_snr")
     s, h = d.sampler, d.hparams
     out, x0, noise, t = _inputs(s, par, seed=3, decoder=decoder)
@@ -247,7 +247,7 @@ def test_cpu_branch_against_float64_restatement(par, kind, decoder):
 
 @pytest.mark.parametrize("par", PARS)
 def test_exact_target_and_min_variance_give_zero_bound(par):
-    from sgdm_amd.train import lv_loss
+    from sgdm_amd.losses import lv_loss
     d = _diffusion(learn_sigma=True, parameterization=par)
     s, h = d.sampler, d.hparams
     _, x0, noise, t = _inputs(s, par, seed=5)
@@ -279,7 +279,7 @@ def test_gradient_stops_at_the_mean(par, kind):
 
 
 def test_gradcheck_of_both_terms():
-    from sgdm_amd.train import lv_decoder_bits, lv_kl_bits
+    from sgdm_amd.losses import lv_decoder_bits, lv_kl_bits
     g = torch.Generator().manual_seed(11)
     r = lambda *sh: torch.randn(*sh, generator=g, dtype=torch.float64)
     mu_th, mu_q = r(12).requires_grad_(True), r(12)

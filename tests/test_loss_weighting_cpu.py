@@ -273,5 +273,5 @@ def test_binding_declares_both_entries_and_the_abi_stays():
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
     assert "loss.hip" in b._sources() and b.FILE_FLAGS["loss.hip"] == ["-ffp-contract=off"]
-    from sgdm_amd.train import _LOSS_KIND, _LOSS_PAR
+    from sgdm_amd.losses import _LOSS_KIND, _LOSS_PAR
     assert _LOSS_PAR == dict(eps=0, x0=1, v=2) and _LOSS_KIND == dict(l2=0, l1=1, huber=2)

@@ -31,7 +31,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from sgdm_amd.diffusion import LatentDiffusion  # noqa: E402
 from sgdm_amd.ema import LitEma  # noqa: E402
-from sgdm_amd.train import _MSEFn, distill_teacher_from  # noqa: E402
+from sgdm_amd.losses import _MSEFn, distill_teacher_from  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=40)
