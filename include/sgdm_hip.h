@@ -813,6 +813,34 @@ int sgd_distill_loss_bwd(const float* out, const float* teach, int32_t cfg_mode,
                          const float* gper /* DEVICE [b]: dL / d per_w */, float gscale, float* gout /* [b, c, hw] */,
                          void* stream);
 
+/* Progressive distillation (csrc/progressive.hip; hparam progressive_steps = K, sgdm_amd/losses.py; Salimans & Ho 2022,
+ * Algorithm 2 = stage 2 of Meng et al. 2023; additive entries, no counterpart in the reference): the student's ONE DDIM step
+ * t -> e on the K-step trailing grid is trained to land where TWO steps t -> m -> e of a frozen teacher land.  `rows` is a DEVICE
+ * table of K rows (sgdm_amd/diffusion.py: progressive_rows, float64 on the host, rounded once), `idx` DEVICE int64 [b], each in
+ * [0, K): the grid index of a sample (the caller's duty: the entries cannot know K).  With g = guided(teach, cfg_mode, *w_dev)
+ * (as sgd_distill_loss_fwd: teach the teacher engine's RAW output, NHWC [2b, hw, c] when cfg_mode != 0, else [b, hw, c]) and r =
+ * rows[idx[n]], every product rounded before it is added:
+ * sgd_pd_half_step: z_mid = r.a1 * x + r.b1 * g (the teacher's first step, z_t -> z_m) and head = r.d0 * x + r.d1 * g (the part
+ *   of the target known after the first evaluation), both NCHW [b, c, hw] like x, from one pass over x and teach.
+ * sgd_pd_loss_fwd / sgd_pd_loss_bwd: sgd_distill_loss_fwd / _bwd with target = head + r.d2 * g, g now the guided output of the
+ *   teacher's SECOND evaluation (at z_mid), read where its engine left it; the target is never written.  t DEVICE int64 [b] is
+ *   the (snapped) timestep wt is gathered with.  per_raw / per_w / gout, kind, gper and gscale as sgd_distill_loss_fwd / _bwd:
+ *   one workgroup per sample and a fixed fold order forward, no by-value argument that depends on the step.
+ * A thread owns pixels and loops over the channels; 16-byte accesses when hw % 4 == 0 and every NCHW tensor of the call is
+ * 16-byte aligned, one float per lane otherwise.  SGD_ERR_ARG, nothing launched: b, c or hw <= 0, cfg_mode / kind out of range, a
+ * NULL pointer the call needs (idx and rows always; w_dev when cfg_mode != 0; wt may be NULL = 1). */
+typedef struct sgd_pd_row { float a1, b1, d0, d1, d2, pad0, pad1, pad2; } sgd_pd_row;
+int sgd_pd_half_step(const float* x /* [b, c, hw] */, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* idx,
+                     const sgd_pd_row* rows, int32_t b, int32_t c, int32_t hw, float* z_mid /* [b, c, hw] */,
+                     float* head /* [b, c, hw] */, void* stream);
+int sgd_pd_loss_fwd(const float* out, const float* head, const float* teach, int32_t cfg_mode, const float* w_dev,
+                    const int64_t* idx, const sgd_pd_row* rows, const int64_t* t, const float* wt /* [T] or NULL = 1 */,
+                    int32_t kind, int32_t b, int32_t c, int32_t hw, float* per_raw /* [b] */, float* per_w /* [b] */, void* stream);
+int sgd_pd_loss_bwd(const float* out, const float* head, const float* teach, int32_t cfg_mode, const float* w_dev,
+                    const int64_t* idx, const sgd_pd_row* rows, const int64_t* t, const float* wt, int32_t kind, int32_t b,
+                    int32_t c, int32_t hw, const float* gper /* DEVICE [b]: dL / d per_w */, float gscale,
+                    float* gout /* [b, c, hw] */, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * Optimizer step: AdamW (lightning_module_common.py:20-42: torch.optim.AdamW defaults, decoupled weight decay)
  * and the LitEma shadow update (dynamic/ema.py:25-44) of every parameter in ONE launch:

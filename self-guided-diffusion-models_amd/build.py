@@ -48,8 +48,11 @@ FILE_FLAGS["lvstep.hip"] = ["-ffp-contract=off"]
 # distill.hip: the same -- the guided target of the distillation loss (sgd_distill_loss_fwd / sgd_distill_loss_bwd) carries the
 # bits of sgd_cfg_guide, product by product
 FILE_FLAGS["distill.hip"] = ["-ffp-contract=off"]
-# (loss.hip, lvloss.hip and distill.hip share csrc/loss_common.h, which is compiled under the includer's flags: the three
-# entries above stand or fall together)
+# progressive.hip: the same -- the teacher's half step and the target of the progressive-distillation loss (sgd_pd_half_step,
+# sgd_pd_loss_fwd / sgd_pd_loss_bwd), product by product
+FILE_FLAGS["progressive.hip"] = ["-ffp-contract=off"]
+# (loss.hip, lvloss.hip, distill.hip and progressive.hip share csrc/loss_common.h, which is compiled under the includer's flags:
+# the four entries above stand or fall together)
 
 
 def _sources():

@@ -82,16 +82,8 @@ __global__ __launch_bounds__(LOSS_BWD_THREADS) void distill_bwd_kernel(const flo
     }
 }
 
-bool distill_args_ok(const float* out, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* t, int32_t kind,
-                     int32_t b, int32_t c, int32_t hw) {
-    if (!out || !teach || !t || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2 || kind < 0 || kind > 2) return false;
-    if (cfg_mode != 0 && !w_dev) return false;
-    return (long)c * hw <= INT32_MAX && 2L * b <= INT32_MAX;
-}
-
-// the 16-byte path: a whole number of pixel quads per plane, `out` and `gout` on a 16-byte boundary (the teacher is read float by
-// float and may sit anywhere)
-bool distill_vec_ok(const float* out, int32_t hw, const float* gout) { return hw % 4 == 0 && aligned16(out) && aligned16(gout); }
+// (the argument rules and the 16-byte path's are csrc/loss_common.h's, shared with progressive.hip: guided_loss_args_ok,
+// guided_loss_vec_ok)
 
 }  // namespace
 
@@ -99,8 +91,8 @@ extern "C" int sgd_distill_loss_fwd(const float* out, const float* teach, int32_
                                     const float* wt, int32_t kind, int32_t b, int32_t c, int32_t hw, float* per_raw, float* per_w,
                                     void* stream) {
     SGD_CLEAR_ERR();
-    if (!distill_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !per_raw || !per_w) return SGD_ERR_ARG;
-    return loss_launch(distill_vec_ok(out, hw, nullptr), distill_fwd_kernel<4>, distill_fwd_kernel<1>, (unsigned)b,
+    if (!guided_loss_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !per_raw || !per_w) return SGD_ERR_ARG;
+    return loss_launch(guided_loss_vec_ok(hw, out), distill_fwd_kernel<4>, distill_fwd_kernel<1>, (unsigned)b,
                        LOSS_FWD_THREADS, stream, out, teach, cfg_mode, w_dev, t, wt, kind, b, c, hw, per_raw, per_w);
 }
 
@@ -108,8 +100,8 @@ extern "C" int sgd_distill_loss_bwd(const float* out, const float* teach, int32_
                                     const float* wt, int32_t kind, int32_t b, int32_t c, int32_t hw, const float* gper,
                                     float gscale, float* gout, void* stream) {
     SGD_CLEAR_ERR();
-    if (!distill_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !gper || !gout) return SGD_ERR_ARG;
-    const bool vec = distill_vec_ok(out, hw, gout);
+    if (!guided_loss_args_ok(out, teach, cfg_mode, w_dev, t, kind, b, c, hw) || !gper || !gout) return SGD_ERR_ARG;
+    const bool vec = guided_loss_vec_ok(hw, out, gout);
     const unsigned bps = loss_bps(vec, hw, b);
     if (!bps) return SGD_ERR_ARG;
     return loss_launch(vec, distill_bwd_kernel<4>, distill_bwd_kernel<1>, bps * b, LOSS_BWD_THREADS, stream, out, teach, cfg_mode,

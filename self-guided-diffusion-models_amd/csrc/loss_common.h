@@ -1,11 +1,12 @@
 // The device core shared by the fused loss pairs: loss.hip (sgd_loss_fwd / sgd_loss_bwd), lvloss.hip (sgd_lv_loss_fwd /
-// sgd_lv_loss_bwd) and distill.hip (sgd_distill_loss_fwd / sgd_distill_loss_bwd).  They differ in the target they form and in
-// what else they compute per element; what an element of the simple term costs, its gradient, the order in which a sample's
-// elements are summed and the launch arithmetic are the same, and live here once: the simple terms of the three pairs agree bit
-// for bit because they ARE the same code, which the tests assert (tests/test_hip_learned_variance.py, tests/test_hip_distill.py).
+// sgd_lv_loss_bwd), distill.hip (sgd_distill_loss_fwd / sgd_distill_loss_bwd) and progressive.hip (sgd_pd_loss_fwd /
+// sgd_pd_loss_bwd).  They differ in the target they form and in what else they compute per element; what an element of the
+// simple term costs, its gradient, the order in which a sample's elements are summed and the launch arithmetic are the same, and
+// live here once: the simple terms of the pairs agree bit for bit because they ARE the same code, which the tests assert
+// (tests/test_hip_learned_variance.py, tests/test_hip_distill.py, tests/test_hip_progressive.py).
 //
 // Everything here is __device__ __forceinline__ (or host inline) and is therefore compiled under the flags of the file that
-// includes it.  All three includers are -ffp-contract=off (build.py: FILE_FLAGS): every product is rounded before it is added,
+// includes it.  All four includers are -ffp-contract=off (build.py: FILE_FLAGS): every product is rounded before it is added,
 // so the gradient reproduces a torch-fp32 restatement bit for bit.  A file compiled with contraction on must not include this.
 #pragma once
 #include "sgdm_common.h"
@@ -66,6 +67,21 @@ __device__ __forceinline__ void loss_store(float* __restrict__ p, long i, loss_v
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The argument rules of the pairs whose target is a GUIDED teacher output (distill.hip, progressive.hip): `out` NCHW [b, c, hw],
+// `teach` NHWC [2b | b, hw, c] read through guided() (csrc/sampler_common.h), the weight from device memory.
+inline bool guided_loss_args_ok(const float* out, const float* teach, int32_t cfg_mode, const float* w_dev, const int64_t* t,
+                                int32_t kind, int32_t b, int32_t c, int32_t hw) {
+    if (!out || !teach || !t || b <= 0 || c <= 0 || hw <= 0 || cfg_mode < 0 || cfg_mode > 2 || kind < 0 || kind > 2) return false;
+    if (cfg_mode != 0 && !w_dev) return false;
+    return (long)c * hw <= INT32_MAX && 2L * b <= INT32_MAX;
+}
+
+// their 16-byte path: a whole number of pixel quads per plane, every NCHW tensor on a 16-byte boundary (NULL: not part of the
+// call; the teacher is read float by float and may sit anywhere)
+inline bool guided_loss_vec_ok(int32_t hw, const float* p0, const float* p1 = nullptr, const float* p2 = nullptr) {
+    return hw % 4 == 0 && aligned16(p0) && aligned16(p1) && aligned16(p2);
+}
 
 // the element-wise passes: blocks of LOSS_BWD_THREADS per sample for `per_sample` floats, a thread per quad (vec) or per float;
 // 0 when b samples of that many blocks do not fit a grid

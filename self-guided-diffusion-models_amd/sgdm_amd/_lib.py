@@ -176,6 +176,10 @@ SIGNATURES = {
     "sgd_ddpm_lv_step": (i32, [vp, vp, vp, i32, f32, dvp, i32, i32, i32, i32, vp, vp, vp]),
     "sgd_distill_loss_fwd": (i32, [vp, vp, i32, dvp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "sgd_distill_loss_bwd": (i32, [vp, vp, i32, dvp, vp, vp, i32, i32, i32, i32, dvp, f32, vp, vp]),
+    # (idx and rows are DEVICE memory the kernels dereference: the table is a [K, 8] fp32 tensor, sgd_pd_row by row)
+    "sgd_pd_half_step": (i32, [vp, vp, i32, dvp, dvp, dvp, i32, i32, i32, vp, vp, vp]),
+    "sgd_pd_loss_fwd": (i32, [vp, vp, vp, i32, dvp, dvp, dvp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "sgd_pd_loss_bwd": (i32, [vp, vp, vp, i32, dvp, dvp, dvp, vp, vp, i32, i32, i32, i32, dvp, f32, vp, vp]),
 }
 
 # include/sgdm_hip_tools.h: the diagnostics library (libsgdm_hip_tools.so) -- bench.py's device calibration, the contention

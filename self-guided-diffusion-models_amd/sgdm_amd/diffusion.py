@@ -33,6 +33,11 @@ Also without a counterpart, guidance distillation (Meng et al. 2023, stage 1): t
 conditional evaluation against the teacher's guided output (include/sgdm_hip.h: sgd_distill_loss_fwd / sgd_distill_loss_bwd); the
 sampling kwarg ``cfg_distilled`` (hparam ``guidance_distilled``) samples such a student with ONE evaluation at B per step, on the
 captured step the batch-B graph alone (``_GraphedStep``: no 2B engine is built).
+Also without a counterpart, progressive distillation (Salimans & Ho 2022, Algorithm 2 = stage 2 of that recipe): the hparam
+``progressive_steps`` = K (``progressive_option``; ``progressive_grid``, ``progressive_rows``: the student's trailing grid and the
+five scalars per grid point with which the target is linear in z_t and the teacher's two outputs) makes ``losses.p_losses_hip``
+train ONE DDIM step of the student against TWO of the frozen teacher (include/sgdm_hip.h: sgd_pd_half_step, sgd_pd_loss_fwd /
+sgd_pd_loss_bwd), ``train.progressive_next_stage`` halves K, and ``p_sample_loop`` walks the student's K steps by default.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -144,6 +149,74 @@ def distill_option(h):
     if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:      # (NaN fails the comparison)
         raise ValueError(f"distill_rescale={phi!r}: a number in [0, 1]")
     return float(w), float(phi)
+
+
+def progressive_option(h):
+    """the optional hparam ``progressive_steps`` = K (None / absent: off; Salimans & Ho 2022, Algorithm 2): the student's step
+    count -- one of its DDIM steps on the K-step trailing grid is trained to land where two steps of the frozen teacher on the
+    2K-step grid land -- validated: None when off, else K.  ValueError for a K that is not a positive int with
+    num_timesteps % (2 K) == 0 (the teacher's midpoints must be timesteps), with learn_sigma and with parameterization 'eps' on
+    a zero-terminal-SNR schedule.  Pure host code."""
+    K = getattr(h, "progressive_steps", None)
+    if K is None:
+        return None
+    T = h.num_timesteps
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 1 or T % (2 * int(K)) != 0:
+        raise ValueError(f"progressive_steps={K!r}: a positive int K with num_timesteps % (2 K) == 0 (num_timesteps is {T}), "
+                         "or None")
+    if getattr(h, "learn_sigma", False):
+        raise ValueError("progressive_steps with learn_sigma: distillation of learned-variance models is not implemented")
+    if getattr(h, "zero_terminal_snr", False) and getattr(h, "parameterization", None) == "eps":
+        raise ValueError("progressive_steps with parameterization='eps' on a zero_terminal_snr schedule: the step from the last "
+                         "timestep divides by sqrt(alphas_cumprod) = 0; use 'v' (or 'x0')")
+    return int(K)
+
+
+def progressive_grid(t, K, T):
+    """(idx, snapped t) of timesteps ``t`` (an int tensor or array on [0, T)) on the K-step trailing grid tau_i = (i + 1) *
+    (T // K) - 1: idx = t // (T // K), so exactly T // K values of t fall on each grid point and a uniform t stays uniform"""
+    st = T // K
+    idx = t // st
+    return idx, (idx + 1) * st - 1
+
+
+def progressive_rows(alphas_cumprod, K, par):
+    """float64 [K, 5] rows (a1, b1, d0, d1, d2) of progressive distillation (include/sgdm_hip.h: sgd_pd_row), row i for the grid
+    point t = (i + 1) * st - 1, st = T // K, with the teacher's midpoint m = t - st // 2 and the end e = t - st (e = -1 reads
+    alphas_cumprod[0]: the DDIM sampler's first a_prev, ``make_ddim_sampling_parameters``).  A deterministic DDIM step t -> s is
+    z_s = A z_t + B y in the network output y of every parameterization; (a1, b1) are (A, B) of t -> m, and
+    y* = d0 z_t + d1 y1 + d2 y2 is the output with which ONE step t -> e lands where the steps t -> m (on y1) and m -> e (on y2)
+    land.  Written in the half-log-SNR forms lambda = sigma / alpha ('eps'), mu = alpha / sigma ('x0') and the angle
+    phi = atan2(sigma, alpha) ('v'): every |d| <= 1, d1 + d2 == 1 for 'eps' and 'x0', nothing cancels (the textbook form through
+    z_m has coefficients in the hundreds).  'x0' and 'v' never divide by alpha and are finite on a zero-terminal-SNR schedule."""
+    ac = torch.as_tensor(alphas_cumprod).detach().cpu().double().numpy()
+    T, K = ac.shape[0], int(K)
+    if K < 1 or T % (2 * K) != 0:
+        raise ValueError(f"progressive_rows: K={K!r} with {T} timesteps (num_timesteps % (2 K) == 0 is needed)")
+    if par not in ("eps", "x0", "v"):
+        raise NotImplementedError(f"parameterization '{par}'")
+    st = T // K
+    t = (np.arange(K) + 1) * st - 1
+    m, e = t - st // 2, np.maximum(t - st, 0)
+    al, sg = np.sqrt(ac), np.sqrt(1.0 - ac)
+    (at, am, ae), (s_t, sm, se) = (al[t], al[m], al[e]), (sg[t], sg[m], sg[e])
+    if par == "eps":
+        if (at == 0).any():
+            raise ValueError("progressive_rows: parameterization 'eps' divides by sqrt(alphas_cumprod), which is 0 on this schedule")
+        lt, lm, le = s_t / at, sm / am, se / ae
+        a1, b1 = am / at, sm - am * s_t / at
+        d0, d1, d2 = np.zeros(K), (lt - lm) / (lt - le), (lm - le) / (lt - le)
+    elif par == "x0":
+        ut, um, ue = at / s_t, am / sm, ae / se
+        a1, b1 = sm / s_t, am - sm * at / s_t
+        d0, d1, d2 = np.zeros(K), (um - ut) / (ue - ut), (ue - um) / (ue - ut)
+    else:
+        pt, pm, pe = np.arctan2(s_t, at), np.arctan2(sm, am), np.arctan2(se, ae)
+        a1, b1 = am * at + sm * s_t, sm * at - am * s_t
+        D1, D2 = pt - pm, pm - pe
+        s12 = np.sin(D1 + D2)
+        d0, d1, d2 = -np.sin(D1) * np.sin(D2) / s12, np.sin(D1) * np.cos(D2) / s12, np.sin(D2) / s12
+    return torch.tensor(np.stack([a1, b1, d0, d1, d2], 1), dtype=torch.float64)
 
 
 def loss_weight_table(alphas_cumprod_fp32, parameterization, scheme, gamma=5.0, k=1.0):
@@ -1581,6 +1654,9 @@ class LatentDiffusion(nn.Module):
         # optional hparams (not in the reference; Meng et al. 2023, stage 1): the training target is the guided output of a
         # frozen teacher (set_distill_teacher; sgdm_amd/losses.py)
         self.distill = distill_option(h)
+        # optional hparam (not in the reference; Salimans & Ho 2022 = stage 2 of that recipe): the training target is the
+        # output with which one DDIM step of the K-step grid lands where two steps of the frozen teacher land
+        self.progressive = progressive_option(h)
         self.sampler_list = {
             "native": self.sampler,
             "ddim": DDIMSampler(ddpm_num_timesteps=h.num_timesteps, device=h.device, sampler_type="ddim"),
@@ -1611,6 +1687,18 @@ class LatentDiffusion(nn.Module):
         .train() of this module.  None removes it."""
         object.__setattr__(self, "_distill_teacher", teacher)
         self.__dict__.pop("_distill_runner", None)
+
+    def progressive_rows_dev(self, dev):
+        """the device table of progressive distillation (include/sgdm_hip.h: sgd_pd_row, [K, 8] fp32): ``progressive_rows``
+        rounded once, uploaded once per (K, schedule, parameterization, device)"""
+        K, par = self.progressive, self.hparams.parameterization
+        key = (K, getattr(self.sampler, "_sched_key", None), par, dev)
+        cache = self.__dict__.setdefault("_pd_rows", {})
+        if key not in cache:
+            tab = torch.zeros(K, 8, dtype=torch.float32)
+            tab[:, :5] = progressive_rows(self.sampler.alphas_cumprod, K, par).float()
+            cache[key] = tab.to(dev).contiguous()
+        return cache[key]
 
     def forward_tao(self, x, **kwargs):
         return self.forward(x, **kwargs)
@@ -1667,6 +1755,11 @@ class LatentDiffusion(nn.Module):
                 sk.setdefault("v_form", "data")
         if getattr(self.hparams, "guidance_distilled", False):      # a distilled student: one conditional evaluation per step
             sk.setdefault("cfg_distilled", True)
+        # a progressively distilled student (hparam progressive_steps = K) is sampled where it was trained: K deterministic
+        # DDIM steps on the trailing grid, one conditional evaluation each; an explicit kwarg still wins
+        if self.progressive is not None and sampling_method in ("ddim", "dpmsolver"):
+            for k, v in dict(num_timesteps=self.progressive, ddim_eta=0, timestep_spacing="trailing", cfg_distilled=True).items():
+                sk.setdefault(k, v)
         native_steps_option(sk, sampling_method, self.hparams.num_timesteps)     # refused on every other sampler
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(

@@ -14,9 +14,16 @@ step (``_loss_path``):
   * ``"distill_fused"``, hparam ``distill_guidance`` with a drop-in UNet teacher on the device (not in the reference; Meng et
     al. 2023, stage 1): the loss against the guided output of a frozen teacher and its gradient = ``sgd_distill_loss_fwd`` /
     ``sgd_distill_loss_bwd`` (``_DistillLossFn``), the target formed on the fly from the raw output the teacher's doubled
-    evaluation left in its engine.  Any other teacher gives a target tensor and the ``"torch"`` path.
+    evaluation left in its engine.  Any other teacher gives a target tensor and the ``"torch"`` path;
+  * ``"progressive_fused"``, hparam ``progressive_steps`` = K with a drop-in UNet teacher on the device (not in the reference;
+    Salimans & Ho 2022, Algorithm 2 = stage 2 of Meng et al. 2023): ``t`` is snapped to the K-step trailing grid, the frozen
+    teacher is evaluated at (z_t, t), ``sgd_pd_half_step`` forms its DDIM half step z_m and the part of the target known so
+    far, the teacher is evaluated again at (z_m, t - T / 2K), and the loss against y* = d0 z_t + d1 y1 + d2 y2 and its gradient
+    = ``sgd_pd_loss_fwd`` / ``sgd_pd_loss_bwd`` (``_ProgressiveLossFn``), the target formed on the fly.  With
+    ``distill_guidance`` as well each teacher evaluation is the guided one (stages 1 and 2 in one).  Any other teacher: the
+    same target as a torch chain (``progressive_target_torch``) and the ``"torch"`` path.
 
-The three kernel pairs share their device core (csrc/loss_common.h).
+The four kernel pairs share their device core (csrc/loss_common.h).
 """
 import ctypes as C
 import math
@@ -158,6 +165,67 @@ class _DistillLossFn(torch.autograd.Function):
         return (gout,) + (None,) * 6
 
 
+# ---- progressive distillation (hparam progressive_steps; Salimans & Ho 2022, Algorithm 2): the target is the output with which
+# ONE DDIM step of the student lands where TWO steps of the frozen teacher land, linear in z_t and the teacher's two outputs
+# (diffusion.progressive_rows).
+class _ProgressiveLossFn(torch.autograd.Function):
+    """_DistillLossFn with target = head + d2 * guided(teacher's second raw output): (per_w, per_raw) in one launch
+    (sgd_pd_loss_fwd), the gradient for the student's output in one more (sgd_pd_loss_bwd).  ``head`` = d0 z_t + d1 y1 is
+    sgd_pd_half_step's; ``teach`` is the teacher engine's own output buffer after its SECOND evaluation, read in place: the
+    target is never written.  The backward reads the buffer again (the rule of _DistillLossFn)."""
+
+    @staticmethod
+    def forward(ctx, out, head, teach, mode, w_dev, idx, rows, t, wt, kind):
+        lib = L.load()
+        out = out.contiguous().float()
+        B, Cc, hw = out.shape[0], out.shape[1], out[0, 0].numel()
+        per_raw, per_w = (torch.empty(B, dtype=torch.float32, device=out.device) for _ in range(2))
+        L.check(lib.sgd_pd_loss_fwd(_ptr(out), _ptr(head), _ptr(teach), mode, _ptr(w_dev), idx.data_ptr(), rows.data_ptr(), _ptr(t),
+                                    _ptr(wt), kind, B, Cc, hw, _ptr(per_raw), _ptr(per_w),
+                                    torch.cuda.current_stream().cuda_stream), "sgd_pd_loss_fwd")
+        ctx.save_for_backward(out, head, teach, w_dev, idx, rows, t, wt)
+        ctx.mode, ctx.kind = mode, kind
+        ctx.mark_non_differentiable(per_raw)
+        return per_w, per_raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, _graw):
+        out, head, teach, w_dev, idx, rows, t, wt = ctx.saved_tensors
+        gper = gper.contiguous().float()
+        gout = torch.empty_like(out)
+        L.check(L.load().sgd_pd_loss_bwd(_ptr(out), _ptr(head), _ptr(teach), ctx.mode, _ptr(w_dev), idx.data_ptr(), rows.data_ptr(),
+                                         _ptr(t), _ptr(wt), ctx.kind, out.shape[0], out.shape[1], out[0, 0].numel(),
+                                         gper.data_ptr(), 1.0, _ptr(gout), torch.cuda.current_stream().cuda_stream),
+                "sgd_pd_loss_bwd")
+        return (gout,) + (None,) * 9
+
+
+def progressive_half_step(x, teach, mode, w_dev, idx, rows):
+    """(z_mid, head) = (a1 x + b1 g, d0 x + d1 g), g = guided(teach), rows gathered at ``idx``: sgd_pd_half_step, one pass over
+    ``x`` (contiguous fp32 NCHW) and the teacher's raw output"""
+    B, Cc, hw = x.shape[0], x.shape[1], x[0, 0].numel()
+    z_mid, head = torch.empty_like(x), torch.empty_like(x)
+    L.check(L.load().sgd_pd_half_step(_ptr(x), _ptr(teach), mode, _ptr(w_dev), idx.data_ptr(), rows.data_ptr(), B, Cc, hw,
+                                      _ptr(z_mid), _ptr(head), torch.cuda.current_stream().cuda_stream), "sgd_pd_half_step")
+    return z_mid, head
+
+
+def progressive_target_torch(rows, idx, x, teacher_eval, t, t_mid):
+    """the target of progressive distillation as a torch chain, in the dtype of ``x``: ``rows`` [K, >= 5] (a1, b1, d0, d1, d2),
+    ``teacher_eval(z, t)`` the teacher's (guided) output.  The CPU branch of p_losses and the restatement the kernels are
+    tested against: z_m = a1 x + b1 y1, head = d0 x + d1 y1, y* = head + d2 y2, in the kernels' order"""
+    r = rows.to(x.device, x.dtype)[idx]
+    a1, b1, d0, d1, d2 = (r[:, k].reshape(-1, *((1,) * (x.dim() - 1))) for k in range(5))
+    y1 = teacher_eval(x, t)
+    z_mid = a1 * x + b1 * y1
+    head = d0 * x + d1 * y1
+    y2 = teacher_eval(z_mid, t_mid)
+    if y2.shape != x.shape:
+        raise ValueError(f"distillation: the teacher's output is {tuple(y2.shape)}, the image {tuple(x.shape)}")
+    return head + d2 * y2
+
+
 def distill_teacher_from(model, ema=None, hip_precision=None):
     """a frozen teacher for guidance distillation from a drop-in UNet: a deep copy of ``model`` (parameters and buffers; no
     engine, workspace or captured step is copied -- the teacher builds its own), with the EMA shadows copied in when ``ema``
@@ -193,11 +261,12 @@ def _distill_setup(diff, student, kwargs, device):
     require grad; a caller's cond_drop_mask (the student is trained on its conditional branch alone); distill_rescale off
     the fused path (the rescale needs both halves of the teacher's doubled evaluation)."""
     from .unet import UNetModelBase
-    w, phi = diff.distill
+    # (progressive_steps without distill_guidance: w is None -- the teacher is evaluated once, conditionally, not guided)
+    w, phi = diff.distill if diff.distill is not None else (None, 0.0)
     teacher = getattr(diff, "_distill_teacher", None)
     if teacher is None:
-        raise ValueError("distill_guidance is set but there is no teacher: call set_distill_teacher(teacher) first "
-                         "(sgdm_amd.train.distill_teacher_from copies one from a drop-in UNet)")
+        raise ValueError(f"{'distill_guidance' if w is not None else 'progressive_steps'} is set but there is no teacher: call "
+                         "set_distill_teacher(teacher) first (sgdm_amd.train.distill_teacher_from copies one from a drop-in UNet)")
     owner = getattr(teacher, "__self__", teacher)
     if owner is student or teacher is diff.denoise_fn or owner is diff.denoise_fn:
         raise ValueError("distillation: teacher and student are the same object; the teacher must be a frozen copy "
@@ -218,6 +287,8 @@ def _distill_setup(diff, student, kwargs, device):
     unet = owner if isinstance(owner, UNetModelBase) and device.type == "cuda" else None
     if unet is not None and getattr(teacher, "__name__", "forward_with_cond_scale") != "forward_with_cond_scale":
         unet = None                                 # some other bound method of a UNet: called as it is
+    if w is None and unet is None:                  # one plain evaluation: the teacher itself, called without a weight
+        return w, phi, unet, teacher
     if phi > 0 and unet is None:
         raise ValueError("distill_rescale needs the fused path: a drop-in UNet teacher on the device (the rescale reads both "
                          "halves of its doubled evaluation)")
@@ -228,13 +299,22 @@ def _distill_setup(diff, student, kwargs, device):
 def _distill_teacher_eval(diff, unet, w, phi, x_noisy, t, kwargs):
     """the fused path: the teacher's doubled evaluation under no_grad, its raw output left where the engine wrote it.
     Returns (teach buffer, cfg_mode, device float w): ``eng.eps_nhwc`` [2B, hw, C] with the teacher's scale type, or with
-    distill_rescale the guide pass's [B, hw, C] and mode 0."""
+    distill_rescale the guide pass's [B, hw, C] and mode 0; with ``w`` None (progressive distillation without
+    distill_guidance) ONE conditional evaluation: ``eng.eps_nhwc`` [B, hw, C], mode 0 and no weight."""
     from .diffusion import _StepRunner
     runner = diff.__dict__.get("_distill_runner")
     if runner is None or runner.model is not unet:
-        runner = diff.__dict__["_distill_runner"] = _StepRunner(unet.forward_with_cond_scale, dict(cond_scale=w))
+        runner = diff.__dict__["_distill_runner"] = _StepRunner(
+            unet.forward_with_cond_scale, *((dict(cond_scale=w),) if w is not None else ({}, dict(cfg_distilled=True))))
         runner.w_dev = {}
     dev = x_noisy.device
+    if w is None:
+        # progressive distillation of an already distilled teacher: ONE conditional evaluation at B, mode 0, no weight (the
+        # evaluation a cfg_distilled sampling step runs: _StepRunner.eps)
+        with torch.no_grad():
+            mask = unet._draw_mask(x_noisy.shape[0], 0.0, dev) if runner.cond_only_mask() else None
+            eng = unet._run(x_noisy, t, kwargs.get("cond"), kwargs.get("layout"), mask, x_noisy.shape[0])
+        return eng.eps_nhwc, 0, None
     if dev not in runner.w_dev:
         runner.w_dev[dev] = torch.full((1,), w, dtype=torch.float32, device=dev)
     w_dev = runner.w_dev[dev]
@@ -391,13 +471,16 @@ def lv_terms(diff, x_start, t, noise, cond_kwargs):
     return lv_loss(s, h, out, x0, nz, tt, weights)
 
 
-def _loss_path(lv, distilling, distill_unet, weights, on_dev):
+def _loss_path(lv, distilling, distill_unet, weights, on_dev, progressive=False):
     """which reduction of the model output a step runs (the module docstring), one value decided before the first launch.
     Only "torch" reads a target tensor; the others form theirs inside their kernels ("lv": inside lv_loss, which has a torch
     branch of its own off the device).  A distillation step never takes "weighted_fused": those kernels form the TRAINED
-    target, not the teacher's; with a teacher that is not a drop-in UNet on the device it is "torch" on the teacher's tensor."""
+    target, not the teacher's; with a teacher that is not a drop-in UNet on the device it is "torch" on the teacher's tensor.
+    ``progressive`` (hparam progressive_steps, with or without distill_guidance): the same rule with the two-step target."""
     if lv:
         return "lv"
+    if progressive:                     # (refused with learned variance: diffusion.progressive_option)
+        return "progressive_fused" if distill_unet is not None else "torch"
     if distilling:
         return "distill_fused" if distill_unet is not None else "torch"
     return "weighted_fused" if weights is not None and on_dev else "torch"
@@ -417,6 +500,12 @@ def per_sample_loss(path, kind, diff, model_output, target, teach, dev, x_start,
             raise ValueError(f"distillation: the student's output is {tuple(model_output.shape)}, the image "
                              f"{tuple(x_start.shape)}")
         per_w, raw = _DistillLossFn.apply(model_output, *teach, dev[2], weights, kind)
+        return per_w, raw if weights is not None else None, None
+    if path == "progressive_fused":
+        if model_output.shape != x_start.shape:
+            raise ValueError(f"distillation: the student's output is {tuple(model_output.shape)}, the image "
+                             f"{tuple(x_start.shape)}")
+        per_w, raw = _ProgressiveLossFn.apply(model_output, *teach, dev[2], weights, kind)
         return per_w, raw if weights is not None else None, None
     if path == "weighted_fused":
         per_w, raw = _WeightedLossFn.apply(model_output, *dev, s.sqrt_alphas_cumprod, s.sqrt_one_minus_alphas_cumprod, weights,
@@ -446,7 +535,12 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     weights = s.loss_weights if getattr(s, "loss_weighting", None) is not None else None
     # hparam distill_guidance: the target is the guided output of the frozen teacher, in the model's own output space; the
     # student is trained on its conditional evaluation alone (cond_drop_prob forced to 0)
+    # hparam progressive_steps = K: the target is the output with which one DDIM step of the K-step trailing grid lands where
+    # two steps of the frozen teacher land; with distill_guidance each teacher evaluation is the guided one, without it ONE
+    # conditional evaluation (the teacher is a distilled student already).  Either way the student trains as in stage 1.
+    prog = getattr(diff, "progressive", None)
     dist = getattr(diff, "distill", None)
+    dist = dist if dist is not None or prog is None else (None, 0.0)        # (no weight, no rescale: _distill_setup)
     d_unet = None
     if dist is not None:
         d_w, d_phi, d_unet, d_fn = _distill_setup(diff, fn, kwargs, x_start.device)
@@ -454,7 +548,13 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
             raise ValueError(f"distillation: the teacher has {d_unet.out_channels} output channels, the image {x_start.shape[1]}")
         kwargs = dict(kwargs, cond_drop_prob=0.0)
     # ---- 2. the loss path
-    path = _loss_path(getattr(s, "learn_sigma", False), dist is not None, d_unet, weights, on_dev)
+    path = _loss_path(getattr(s, "learn_sigma", False), dist is not None, d_unet, weights, on_dev, prog is not None)
+    if prog is not None:
+        # t snapped to the student's grid, on the device: what q_sample, both models, the weights and the logs see
+        from .diffusion import progressive_grid
+        T = h.num_timesteps
+        p_idx, t = progressive_grid(t.to(torch.int64), prog, T)
+        p_idx, t, t_mid = p_idx.contiguous(), t.contiguous(), t - (T // prog) // 2
     # ---- 3. noise; the v target as a tensor only where a torch chain will read it
     want_v = path == "torch" and par == "v" and dist is None
     dev = target = None
@@ -471,10 +571,29 @@ def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     teach = None
     if path == "distill_fused":
         teach = _distill_teacher_eval(diff, d_unet, d_w, d_phi, x_noisy, dev[2], kwargs)
+    elif path == "progressive_fused":
+        # teacher at (z_t, t); its half step z_m and the head of the target in one pass; teacher at (z_m, m).  The second
+        # evaluation overwrites the first's output in the engine: the head is all the loss needs of it.
+        rows = diff.progressive_rows_dev(x_noisy.device)
+        teach1, mode, w_dev = _distill_teacher_eval(diff, d_unet, d_w, d_phi, x_noisy, dev[2], kwargs)
+        z_mid, head = progressive_half_step(x_noisy, teach1, mode, w_dev, p_idx, rows)
+        teach2, mode, w_dev = _distill_teacher_eval(diff, d_unet, d_w, d_phi, z_mid, t_mid, kwargs)
+        teach = head, teach2, mode, w_dev, p_idx, rows
     elif dist is not None:
         with torch.no_grad():
             ckw = {k: kwargs[k] for k in ("layout",) if k in kwargs}
-            target = d_fn(x_noisy, t, d_w, cond=kwargs.get("cond"), **ckw).detach()
+            if d_w is not None:
+                teacher_eval = lambda z, tt: d_fn(z, tt, d_w, cond=kwargs.get("cond"), **ckw)
+            else:                                   # a plain evaluation; a model's (output, loss, dict) triple is accepted
+                def teacher_eval(z, tt):
+                    y = d_fn(z, tt, cond=kwargs.get("cond"), **ckw)
+                    return y[0] if isinstance(y, (tuple, list)) else y
+            if prog is None:
+                target = teacher_eval(x_noisy, t).detach()
+            else:
+                from .diffusion import progressive_rows
+                rows = progressive_rows(s.alphas_cumprod, prog, par).float()
+                target = progressive_target_torch(rows, p_idx, x_noisy, teacher_eval, t, t_mid).detach()
     # ---- 5. the student
     model_output, loss_inside, dict_inside = diff.denoise_fn(x_noisy, t, *args, **kwargs)
     prefix = "train" if diff.training else "val"

@@ -16,7 +16,8 @@ walking the forward tape in reverse:
 
 The losses whose ``backward()`` starts this program -- q_sample, the fused loss kernels, ``p_losses_hip`` -- are ``losses.py``;
 ``distill_teacher_from`` is re-exported here, the name the documentation and the error messages give it, and so are the
-names callers took from this module before the move.
+names callers took from this module before the move.  ``progressive_next_stage`` (progressive distillation: the student becomes
+the next teacher, the step count is halved) lives here, next to the name it builds the teacher with.
 
 ``loss.backward()`` works because the UNet evaluation is a ``torch.autograd.Function`` whose inputs are the
 trainable parameters; it returns one gradient tensor per parameter in the reference layout.
@@ -40,6 +41,32 @@ from .losses import distill_teacher_from  # noqa: F401  (sgdm_amd.train.distill_
 from .losses import (_LOSS_KIND, _LOSS_PAR, _MSEFn, _lv_tables, lv_decoder_bits, lv_kl_bits, lv_loss, lv_terms,  # noqa: F401
                      lv_vlb_torch, p_losses_hip, simple_loss_torch as _simple_torch)
 from .unet import GN_EPS, GN_GROUPS, _Program, _ptr
+
+
+def progressive_next_stage(diff, ema=None, hip_precision=None):
+    """the next stage of progressive distillation (hparam progressive_steps = K; Salimans & Ho 2022, Algorithm 2): a frozen
+    copy of the current student (``distill_teacher_from``: the drop-in UNet behind ``diff.denoise_fn``, its EMA shadows when
+    ``ema`` is given, optionally another arithmetic mode) becomes the teacher and K is halved.  The new teacher is a distilled
+    model already, so ``distill_guidance`` / ``distill_rescale`` are cleared (each of its evaluations is ONE conditional one)
+    and ``guidance_distilled`` is set; the cached row table and teacher runner are dropped.  Returns the new K.  ValueError,
+    nothing changed: progressive_steps is off or 1, or num_timesteps % (2 * (K // 2)) != 0 (the next teacher's midpoints would
+    fall between timesteps)."""
+    K, T = getattr(diff, "progressive", None), diff.hparams.num_timesteps
+    if K is None:
+        raise ValueError("progressive_next_stage: progressive_steps is not set")
+    if K == 1:
+        raise ValueError("progressive_next_stage: progressive_steps is 1, there is no stage after a one-step student")
+    if K % 2 != 0 or T % K != 0:
+        raise ValueError(f"progressive_next_stage: progressive_steps={K} cannot be halved: num_timesteps % (2 * (K / 2)) == 0 "
+                         f"with an integer K / 2 is needed (num_timesteps is {T})")
+    student = getattr(diff.denoise_fn, "__self__", diff.denoise_fn)
+    teacher = distill_teacher_from(student, ema=ema, hip_precision=hip_precision)
+    h = diff.hparams
+    h.progressive_steps, h.distill_guidance, h.distill_rescale, h.guidance_distilled = K // 2, None, None, True
+    diff.progressive, diff.distill = K // 2, None
+    diff.__dict__.pop("_pd_rows", None)
+    diff.set_distill_teacher(teacher)                   # (drops the teacher runner)
+    return K // 2
 
 
 class _PackedAdj:
