@@ -14,6 +14,12 @@ walking the forward tape in reverse:
     ResBlocks and the identity-skip gradient folded into the apply pass);
   * attention backward = ``sgd_attention_bwd`` with the forward's log-sum-exp (no score matrix stored).
 
+The tape holds ONE record per forward GEMM (``unet._Layer``: descriptor, pack, parameter names, bias padding) and the walk
+derives both adjoints from it: ``gemm_geometry`` reads (cout, cin, taps, rows), the input-gradient geometry and the strided
+adjoint's zero-upsampling off the descriptor; ``Backward.dx(layer, gy, dst)`` is the input gradient, ``Backward.dw(layer, gy)``
+the weight / bias gradient, zero-padded operators (padded attention heads) included.  The per-kind methods (``_res``, ``_attn``,
+...) are the chain rule of their block in those two calls; only the FiLM projection calls ``dgrad`` / ``wgrad`` itself.
+
 The losses whose ``backward()`` starts this program -- q_sample, the fused loss kernels, ``p_losses_hip`` -- are ``losses.py``;
 ``distill_teacher_from`` is re-exported here, the name the documentation and the error messages give it, and so are the
 names callers took from this module before the move.  ``progressive_next_stage`` (progressive distillation: the student becomes
@@ -29,6 +35,7 @@ the LAST forward on that engine: ``_UNetTrainFn.backward`` checks a forward-gene
 forward ran in between (two losses on one model need two backward-before-next-forward passes, as here, or two batches
 of different size).
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -40,7 +47,7 @@ from .losses import distill_teacher_from  # noqa: F401  (sgdm_amd.train.distill_
 # the names callers took from this module while the loss code lived here keep resolving; new code imports them from losses.py
 from .losses import (_LOSS_KIND, _LOSS_PAR, _MSEFn, _lv_tables, lv_decoder_bits, lv_kl_bits, lv_loss, lv_terms,  # noqa: F401
                      lv_vlb_torch, p_losses_hip, simple_loss_torch as _simple_torch)
-from .unet import GN_EPS, GN_GROUPS, _Program, _ptr
+from .unet import GN_EPS, GN_GROUPS, _PackBatch, _Program, _ptr
 
 
 def progressive_next_stage(diff, ema=None, hip_precision=None):
@@ -149,6 +156,26 @@ def wgrad_ksplit(taps, cout, cin, rows):
     return max(1, min(ktiles, 1024 // base))
 
 
+GemmGeometry = collections.namedtuple("GemmGeometry", "cout cin taps rows conv zero_up")
+
+
+def gemm_geometry(a):
+    """what the adjoints of one forward GEMM need, read off its descriptor (an IgemmArgs): the GEMM's (cout, cin, taps, rows);
+    conv: the geometry (n, h, w) of the input-gradient launch, None for a flat (1x1 / linear) launch; zero_up: the adjoint of a
+    strided conv reads gy zero-upsampled x2.  A stride-1 conv with a resample in its loader (RS_AVGPOOL2, RS_UP2) runs its
+    input gradient at the OUTPUT resolution, like any other: the resample's adjoint is the caller's (gn_bwd's gu_mode,
+    sgd_resample_bwd)."""
+    if a.mode == L.MODE_FLAT:
+        return GemmGeometry(a.cout, a.c0 + a.c1, 1, a.m, None, False)
+    return GemmGeometry(a.cout, a.c0 + a.c1, 9, a.n * a.ho * a.wo, (a.n, a.ho, a.wo), a.stride == 2)
+
+
+def _tag(layer):
+    """program tag of a layer's launches: the name of its (one) weight parameter less the ".weight" suffix"""
+    wname, = layer.wnames
+    return wname[:-len(".weight")]
+
+
 class Backward:
     """backward launch program of one engine (unet_fast)"""
 
@@ -174,6 +201,8 @@ class Backward:
         self.keep = []
         self.CW = 256                    # row chunks of the two-stage column sums
         self.cwork = torch.empty(self.CW, 8192, dtype=torch.float32, device=self.dev)
+        self.wscratch_bytes, self._wscratch_buf = 0, None      # pre-split operand planes of the 3x3 weight gradients (wgrad)
+        self._pack_batch = self._flag = self._windows = None
         self._build()
 
     # ---------------------------------------------------------------- helpers
@@ -269,7 +298,6 @@ class Backward:
         self.prog.add(tag, self.lib.sgd_igemm, C.byref(a), flops=2.0 * rows * cout_of_y * (9 if conv is not None else 1) * cin_of_gy)
 
     def wgrad(self, tag, fwd_args, gy, gy_ld, cout, cin, taps, rows, wname, bias_name=None, dw_view=None):
-        ktiles = (rows + 63) // 64
         ksplit = wgrad_ksplit(taps, cout, cin, rows)
         slabs = self.buf(ksplit, taps, cout, cin)
         xt = os.environ.get("SGDM_WGRAD_TUNE")      # A/B switch of tools/profile_train_layers.py: "<SGD_TUNE_WGRAD_* bits>[:max cin*cout]"
@@ -278,7 +306,7 @@ class Backward:
         # 3x3 convs: operands pre-split once into 16-bit planes (scratch shared by every launch of the program, grown to
         # the largest request before the first run: sgd_wgrad_scratch)
         need = int(self.lib.sgd_wgrad_scratch_bytes(C.byref(fwd_args), cout)) if taps == 9 else 0
-        self.wscratch_bytes = max(getattr(self, "wscratch_bytes", 0), need)
+        self.wscratch_bytes = max(self.wscratch_bytes, need)
         # the bias gradient (column sums of gy) comes out of the same launch: the kernel (or its pre-pass) stages the gy
         # rows anyway; as many partial rows as that launch writes
         brows = int(self.lib.sgd_wgrad_bias_rows(C.byref(fwd_args), cout, gy_ld, ksplit, need)) if bias_name is not None else 0
@@ -305,9 +333,42 @@ class Backward:
             self.wrote(bias_name)
 
     def _wscratch(self):
-        if getattr(self, "_wscratch_buf", None) is None or self._wscratch_buf.numel() * 4 < self.wscratch_bytes:
+        if self._wscratch_buf is None or self._wscratch_buf.numel() * 4 < self.wscratch_bytes:
             self._wscratch_buf = torch.empty(max(4, self.wscratch_bytes) // 4 + 4, dtype=torch.float32, device=self.dev)
         return self._wscratch_buf
+
+    # The two adjoints of one forward GEMM, derived from its record (unet._Layer): geometry from the descriptor
+    # (gemm_geometry), the weight and its zero-padded re-layout from the pack, the parameter names from the record.  Tags are
+    # the weight's name without ".weight".  Two calls, not one: the call sites' order is the program order and the
+    # first-use order of pg(name) -- the order of the DDP arena's slots and buckets.
+    def dx(self, layer, gy, dst, acc=False, tag=None):
+        """dst (+)= the gradient of the layer's input, from the gradient gy of its output"""
+        g, pk = gemm_geometry(layer.a), layer.pk
+        w, = pk.srcs
+        src_fn = (lambda: w) if pk.pad is None else (lambda: pk.pad.apply(w.detach().float()))
+        self.dgrad(tag or _tag(layer) + ".dgrad", gy, g.cout, dst, g.cin, pk.srcs, src_fn, g.cout, g.cin,
+                   pk.ksize, conv=g.conv, m=0 if g.conv else g.rows, zero_up=g.zero_up, acc=acc)
+
+    def dw(self, layer, gy):
+        """the layer's weight (and bias) gradient.  A zero-padded operator (unet._Pad; the descriptor's widths are the PADDED
+        ones): the padded gradient is gathered back into the parameter's own shape -- the padding rows / columns receive
+        gradients that belong to no parameter -- and the bias gradient is the column sums of gy, gathered like the weight's
+        rows where the bias is padded too."""
+        g, pad = gemm_geometry(layer.a), layer.pk.pad
+        (wname,), tag = layer.wnames, _tag(layer)
+        if pad is None:
+            return self.wgrad(tag, layer.a, gy, g.cout, g.cout, g.cin, g.taps, g.rows, wname, layer.bias)
+        tmp = self.buf(g.cout, g.cin)
+        self.wgrad(tag, layer.a, gy, g.cout, g.cout, g.cin, g.taps, g.rows, wname, dw_view=tmp)
+        self.gather_op(tag + ".unpad", wname, tmp, pad)
+        if layer.bias is None:
+            return
+        if layer.bias_pad is None:
+            return self.colsum(tag + ".bias", _ptr(gy), g.rows, g.cout, g.cout, layer.bias)
+        tb = self.buf(1, g.cout)
+        self.prog.add(tag + ".bias", self.lib.sgd_colsum, _ptr(gy), g.rows, g.cout, g.cout, _ptr(tb), 0, self.unscale,
+                      _ptr(self.cwork), self.CW)
+        self.gather_op(tag + ".bias.unpad", layer.bias, tb, layer.bias_pad)
 
     def colsum(self, tag, g_ptr, rows, c, ld, pname):
         self.prog.add(tag, self.lib.sgd_colsum, g_ptr, rows, c, ld, _ptr(self.pg(pname)), 0, self.unscale,
@@ -368,26 +429,22 @@ class Backward:
         # (the launcher's bound: dynamic table + the kernel's 2 KB of static reduction scratch inside the 64 KB default limit)
         fused = (n <= 256 and (16 if chunks else 8) * n * (ct // GN_GROUPS) + 32 * n + 4 + 2048 <= 64 * 1024
                  and os.environ.get("SGDM_GN_BWD_FOLD", "1") != "0")
+        coef = (_ptr(S), sch, _ptr(sums), _ptr(gamma), _ptr(beta), C.c_void_p(film_ptr), film_ld, n, ct, GN_GROUPS, h * w,
+                GN_EPS, _ptr(A), _ptr(B), _ptr(Cc))
+        dgamma, dbeta, dfilm = _ptr(self.pg(gname + ".weight")), _ptr(self.pg(gname + ".bias")), C.c_void_p(dfilm_ptr)
+        dg, db = (None, None) if fused else (self.buf(n, ct), self.buf(n, ct))       # per-sample tables of the unfused forms
         if fused:                # coefficients + dgamma / dbeta column sums in ONE launch (bit-identical to the two below)
-            self.prog.add(tag + ".coef", lib.sgd_gn_bwd_coef_fold, _ptr(S), sch, _ptr(sums), _ptr(gamma), _ptr(beta),
-                          C.c_void_p(film_ptr), film_ld, n, ct, GN_GROUPS, h * w, GN_EPS, _ptr(A), _ptr(B), _ptr(Cc),
-                          C.c_void_p(dfilm_ptr), _ptr(self.pg(gname + ".weight")), _ptr(self.pg(gname + ".bias")), 0,
+            self.prog.add(tag + ".coef", lib.sgd_gn_bwd_coef_fold, *coef, dfilm, dgamma, dbeta, 0, self.unscale)
+        elif n <= 256:           # dgamma and dbeta from the per-sample tables in one launch
+            self.prog.add(tag + ".coef", lib.sgd_gn_bwd_coef, *coef, _ptr(dg), _ptr(db), dfilm)
+            self.prog.add(tag + ".dgamma_dbeta", lib.sgd_colsum_pair, _ptr(dg), _ptr(db), n, ct, ct, dgamma, dbeta, 0,
                           self.unscale)
         else:
-            dg, db = self.buf(n, ct), self.buf(n, ct)
-            self.prog.add(tag + ".coef", lib.sgd_gn_bwd_coef, _ptr(S), sch, _ptr(sums), _ptr(gamma), _ptr(beta),
-                          C.c_void_p(film_ptr), film_ld, n, ct, GN_GROUPS, h * w, GN_EPS, _ptr(A), _ptr(B), _ptr(Cc),
-                          _ptr(dg), _ptr(db), C.c_void_p(dfilm_ptr))
-        if fused:
-            pass
-        elif n <= 256:           # dgamma and dbeta from the per-sample tables in one launch
-            self.prog.add(tag + ".dgamma_dbeta", lib.sgd_colsum_pair, _ptr(dg), _ptr(db), n, ct, ct,
-                          _ptr(self.pg(gname + ".weight")), _ptr(self.pg(gname + ".bias")), 0, self.unscale)
-        else:
-            self.prog.add(tag + ".dgamma", lib.sgd_colsum, _ptr(dg), n, ct, ct, _ptr(self.pg(gname + ".weight")), 0,
-                          self.unscale, _ptr(self.cwork), self.CW)
-            self.prog.add(tag + ".dbeta", lib.sgd_colsum, _ptr(db), n, ct, ct, _ptr(self.pg(gname + ".bias")), 0,
-                          self.unscale, _ptr(self.cwork), self.CW)
+            self.prog.add(tag + ".coef", lib.sgd_gn_bwd_coef, *coef, _ptr(dg), _ptr(db), dfilm)
+            self.prog.add(tag + ".dgamma", lib.sgd_colsum, _ptr(dg), n, ct, ct, dgamma, 0, self.unscale, _ptr(self.cwork),
+                          self.CW)
+            self.prog.add(tag + ".dbeta", lib.sgd_colsum, _ptr(db), n, ct, ct, dbeta, 0, self.unscale, _ptr(self.cwork),
+                          self.CW)
         self.wrote(gname + ".weight")
         self.wrote(gname + ".bias")
         off = 0
@@ -402,78 +459,50 @@ class Backward:
 
     # ---------------------------------------------------------------- program
     def _build(self):
-        e, m, n = self.e, self.m, self.n
-        P = m.P
+        e, n = self.e, self.n
         self.geps = self.buf(*e.eps_nhwc.shape)           # filled by the autograd Function before the program runs
         film_rec = [r for r in e.tape if r["kind"] == "film"][0]
         self.gfilm = self.buf(n, film_rec["film_w"])
         self._film_plan(film_rec)
         for rec in reversed(e.tape):
-            kind = rec["kind"]
-            if kind == "head":
-                self._head(rec)
-            elif kind == "res":
-                self._res(rec)
-            elif kind == "attn":
-                self._attn(rec)
-            elif kind == "conv_in":
-                h, w = rec["hw"]
-                gy = self.gread(rec["y"])
-                self.wgrad(rec["p"], rec["a"], gy, rec["cout"], rec["cout"], rec["cin"], 9, n * h * w,
-                           rec["p"] + ".weight", rec["p"] + ".bias")
-            elif kind == "film":
-                self._film(rec)
-            elif kind == "mlp2":
-                self._mlp2(rec)
-            elif kind == "attn_lr":
-                self._attn_lr(rec)
-            elif kind == "down":
-                self._down(rec)
-            elif kind == "up":
-                self._up(rec)
-            elif kind == "norm_cond":
-                self._norm_cond(rec)
-            elif kind == "mlp_chain":
-                self._mlp_chain(rec)
-            elif kind == "linear":
-                gy = self.gread(rec["y"])
-                self.wgrad(rec["name"], rec["a"], gy, rec["cout"], rec["cout"], rec["cin"], 1, n,
-                           rec["name"] + ".weight", rec["name"] + ".bias")
-            else:
-                raise NotImplementedError(kind)
+            step = getattr(self, "_" + rec["kind"], None)
+            if step is None:
+                raise NotImplementedError(rec["kind"])
+            step(rec)
+
+    def _conv_in(self, rec):
+        """the stem: its input is the image, no gradient wanted"""
+        self.dw(rec["a"], self.gread(rec["y"]))
+
+    def _linear(self, rec):
+        """to_cond_tokens.0: its input is the guidance, no gradient wanted"""
+        self.dw(rec["a"], self.gread(rec["y"]))
 
     def _head(self, rec):
-        n, (h, w), c = self.n, rec["hw"], rec["c"]
-        oc = self.m.out_channels
+        x = rec["x"]
+        n, h, w, c = x.shape
         gu = self.buf(n, h, w, c)
-        wt = self.m.P("out.2.weight")
-        self.dgrad("out.2.dgrad", self.geps, oc, gu, c, [wt], lambda: wt, oc, c, 3, conv=(n, h, w))
-        self.wgrad("out.2", rec["conv"], self.geps, oc, oc, c, 9, n * h * w, "out.2.weight", "out.2.bias")
-        self.gn_bwd("out.0", [(rec["x"], c)], (h, w), rec["a"], rec["b"], rec["sums"], "out.0", 1, gu, c, L.RS_NONE,
-                    None, 0, 0)
+        self.dx(rec["conv"], self.geps, gu)
+        self.dw(rec["conv"], self.geps)
+        self.gn_bwd("out.0", [(x, c)], (h, w), rec["a"], rec["b"], rec["sums"], "out.0", 1, gu, c, L.RS_NONE, None, 0, 0)
 
     def _res(self, rec):
-        n, p = self.n, rec["p"]
-        P = self.m.P
-        cin, cout = rec["cin"], rec["cout"]
-        (hh, ww), (ho, wo), rs = rec["hw_in"], rec["hw_out"], rec["rs"]
+        p, e = rec["p"], self.e
+        (hh, ww), rs = rec["hw_in"], rec["rs"]
+        n, ho, wo, cout = rec["h1"].shape
+        cin = sum(c for _, c in rec["srcs"])
         gy = self.gread(rec["y"])
-        rows_o = n * ho * wo
         # conv2 (out_layers.3)
-        w2 = P(p + ".out_layers.3.weight")
         gu2 = self.buf(n, ho, wo, cout)
-        self.dgrad(p + ".out_layers.3.dgrad", gy, cout, gu2, cout, [w2], lambda w2=w2: w2, cout, cout, 3, conv=(n, ho, wo))
-        self.wgrad(p + ".out_layers.3", rec["conv2"], gy, cout, cout, cout, 9, rows_o, p + ".out_layers.3.weight",
-                   p + ".out_layers.3.bias")
+        self.dx(rec["conv2"], gy, gu2)
+        self.dw(rec["conv2"], gy)
         # GN2 + FiLM + SiLU -> gradient of h1 and of this block's FiLM slice
-        e = self.e
-        film_ptr = e.film.data_ptr() + 4 * rec["film_off"]
-        dfilm_ptr = self.gfilm.data_ptr() + 4 * rec["film_off"]
         self.G[rec["h1"].data_ptr()] = [self.buf(*rec["h1"].shape), False]
-        if rec.get("ss", True):
+        if rec["ss"]:
             self.gn_bwd(p + ".out_layers.0", [(rec["h1"], cout)], (ho, wo), rec["a2"], rec["b2"], rec["sums2"],
-                        p + ".out_layers.0", 1, gu2, cout, L.RS_NONE, None, 0, 0, film_ptr=film_ptr, film_ld=e.film_ld,
-                        dfilm_ptr=dfilm_ptr, drop=(rec["drop_p"], rec["drop_seed"]))
+                        p + ".out_layers.0", 1, gu2, cout, L.RS_NONE, None, 0, 0,
+                        film_ptr=e.film.data_ptr() + 4 * rec["film_off"], film_ld=e.film_ld,
+                        dfilm_ptr=self.gfilm.data_ptr() + 4 * rec["film_off"], drop=(rec["drop_p"], rec["drop_seed"]))
             gh1 = self.gread(rec["h1"])
         else:
             # additive embedding (openaimodel.py:317-319): h1 holds h + emb_out; the gradient of emb_out[n, c] is the pixel sum of
@@ -486,19 +515,15 @@ class Backward:
             self.prog.add(p + ".emb_add.bwd", self.lib.sgd_chan_stats, _ptr(gh1), n, ho * wo, cout, _ptr(st), cout, 0)
             self.copy_op(p + ".emb_add.gfilm", self.gfilm[:, rec["film_off"]:rec["film_off"] + cout], st[:, :, 0])
         self._film_group_done(p)
-        # conv1 (in_layers.2)
-        w1 = P(p + ".in_layers.2.weight")
+        # conv1 (in_layers.2): its input gradient at the OUTPUT resolution, the resample's adjoint in GN1's backward below
         gu1 = self.buf(n, ho, wo, cin)
-        self.dgrad(p + ".in_layers.2.dgrad", gh1, cout, gu1, cin, [w1], lambda w1=w1: w1, cout, cin, 3, conv=(n, ho, wo))
-        self.wgrad(p + ".in_layers.2", rec["conv1"], gh1, cout, cout, cin, 9, rows_o, p + ".in_layers.2.weight",
-                   p + ".in_layers.2.bias")
+        self.dx(rec["conv1"], gh1, gu1)
+        self.dw(rec["conv1"], gh1)
         # skip path
         if rec["skip"] is not None:
-            ws = P(p + ".skip_connection.weight")
             gsk = self.buf(n, hh, ww, cin)
-            self.dgrad(p + ".skip.dgrad", gy, cout, gsk, cin, [ws], lambda ws=ws: ws, cout, cin, 1, m=n * hh * ww)
-            self.wgrad(p + ".skip_connection", rec["skip"], gy, cout, cout, cin, 1, n * hh * ww,
-                       p + ".skip_connection.weight", p + ".skip_connection.bias")
+            self.dx(rec["skip"], gy, gsk, tag=p + ".skip.dgrad")
+            self.dw(rec["skip"], gy)
             gres, gres_ld, gres_mode = gsk, cin, L.RS_NONE
         else:
             gres, gres_ld, gres_mode = gy, cout, rs            # identity skip through the same resample
@@ -506,105 +531,60 @@ class Backward:
         self.gn_bwd(p + ".in_layers.0", rec["srcs"], (hh, ww), rec["a1"], rec["b1"], rec["sums1"], p + ".in_layers.0",
                     1, gu1, cin, rs, gres, gres_ld, gres_mode)
 
-    def wgrad_padded(self, tag, fwd, g, cout, cin, nrows, wname, wpad, bias_name=None, bpad=None):
-        """weight (and bias) gradient of a 1x1 / linear layer whose packed operator is a zero-padded re-layout of the parameter
-        (unet._Pad; cout / cin are the PADDED widths): the padded gradient is gathered back into the parameter's own shape -- the
-        padding rows / columns receive gradients that belong to no parameter.  bpad None with a bias: the bias is not padded."""
-        if wpad is None:
-            return self.wgrad(tag, fwd, g, cout, cout, cin, 1, nrows, wname, bias_name)
-        tmp = self.buf(cout, cin)
-        self.wgrad(tag, fwd, g, cout, cout, cin, 1, nrows, wname, None, dw_view=tmp)
-        self.gather_op(tag + ".unpad", wname, tmp, wpad)
-        if bias_name is None:
-            return
-        if bpad is None:
-            return self.colsum(tag + ".bias", _ptr(g), nrows, cout, cout, bias_name)
-        tb = self.buf(1, cout)             # bias gradient = column sums of g, gathered like the weight's rows
-        self.prog.add(tag + ".bias", self.lib.sgd_colsum, _ptr(g), nrows, cout, cout, _ptr(tb), 0, self.unscale,
-                      _ptr(self.cwork), self.CW)
-        self.gather_op(tag + ".bias.unpad", bias_name, tb, bpad)
-
     def _attn(self, rec):
-        """AttentionBlock backward (autograd of openaimodel.py:365-371, 403-420 / 427-451); zero-padded heads (rec["pads"]) as in
-        _attn_lr: every tensor between qkv and proj_out is dp wide per head"""
-        n, p, ch, heads, d, T = self.n, rec["p"], rec["ch"], rec["heads"], rec["d"], rec["T"]
-        dp, pads = rec.get("dp", d), rec.get("pads")
+        """AttentionBlock backward (autograd of openaimodel.py:365-371, 403-420 / 427-451); with zero-padded heads (dp > d) every
+        tensor between qkv and proj_out is dp wide per head, as in _attn_lr"""
+        n, p, ch, heads, d, dp, T = self.n, rec["p"], rec["ch"], rec["heads"], rec["d"], rec["dp"], rec["T"]
         inner = heads * dp
-        P = self.m.P
-        hh, ww = rec["hw"]
         gy = self.gread(rec["y"])
-        adj = lambda w, key: (lambda: w) if pads is None else (lambda: pads[key].apply(w.detach().float()))
-        pad = lambda key: None if pads is None else pads[key]
-        wp = P(p + ".proj_out.weight")
         gatt = self.buf(n, T, inner)
-        self.dgrad(p + ".proj_out.dgrad", gy, ch, gatt, inner, [wp], adj(wp, "out"), ch, inner, 1, m=n * T)
-        self.wgrad_padded(p + ".proj_out", rec["proj_args"], gy, ch, inner, n * T, p + ".proj_out.weight", pad("out"),
-                          p + ".proj_out.bias")
+        self.dx(rec["proj_args"], gy, gatt)
+        self.dw(rec["proj_args"], gy)
         qkv, gqkv = rec["qkv"], self.buf(n, T, 3 * inner)
         dvec = self.buf(n, heads, T)
         off = lambda t, k: C.c_void_p(t.data_ptr() + 4 * k)
-        hs, ko, vo = rec.get("qkv_layout", (3 * d, d, 2 * d))      # head stride, k / v offsets: legacy or new attention order
+        hs, ko, vo = rec["qkv_layout"]                     # head stride, k / v offsets: legacy or new attention order
         self.prog.add(p + ".attn_bwd", self.attention_bwd_fn(dp), _ptr(qkv), 3 * inner, hs, off(qkv, ko), off(qkv, vo),
                       3 * inner, hs, _ptr(rec["att"]), inner, _ptr(gatt), inner, _ptr(rec["lse"]), _ptr(dvec), n, heads, T, T,
                       dp, 1.0 / math.sqrt(d), _ptr(gqkv), off(gqkv, ko), off(gqkv, vo))
-        wq = P(p + ".qkv.weight")
         gxn = self.buf(n, T, ch)
-        self.dgrad(p + ".qkv.dgrad", gqkv, 3 * inner, gxn, ch, [wq], adj(wq, "qkv"), 3 * inner, ch, 1, m=n * T)
-        self.wgrad_padded(p + ".qkv", rec["qkv_args"], gqkv, 3 * inner, ch, n * T, p + ".qkv.weight", pad("qkv"),
-                          p + ".qkv.bias", pad("qkv_bias"))
-        self.gn_bwd(p + ".norm", [(rec["x"], ch)], (hh, ww), rec["a"], rec["b"], rec["sums"], p + ".norm", 0, gxn, ch,
+        self.dx(rec["qkv_args"], gqkv, gxn)
+        self.dw(rec["qkv_args"], gqkv)
+        self.gn_bwd(p + ".norm", [(rec["x"], ch)], rec["hw"], rec["a"], rec["b"], rec["sums"], p + ".norm", 0, gxn, ch,
                     L.RS_NONE, gy, ch, L.RS_NONE)                       # residual: x + proj(...)
 
     def _down(self, rec):
         """Downsample = conv3x3 stride 2 (openaimodel_ca.py:167-174)"""
-        n, p, c = self.n, rec["p"], rec["c"]
-        hh, ww = rec["hw_in"]
         gy = self.gread(rec["y"])
-        w = self.m.P(p + ".op.weight")
         dst, acc = self.gact(rec["x"])
-        self.dgrad(p + ".op.dgrad", gy, c, dst, c, [w], lambda: w, c, c, 3, conv=(n, hh // 2, ww // 2), zero_up=True,
-                   acc=bool(acc))
-        self.wgrad(p + ".op", rec["a"], gy, c, c, c, 9, n * (hh // 2) * (ww // 2), p + ".op.weight", p + ".op.bias")
+        self.dx(rec["a"], gy, dst, acc=bool(acc))
+        self.dw(rec["a"], gy)
 
     def _up(self, rec):
         """Upsample = nearest x2 + conv3x3 (openaimodel_ca.py:128-131)"""
-        n, p, c = self.n, rec["p"], rec["c"]
-        hh, ww = rec["hw_in"]
+        n, hh, ww, c = rec["x"].shape
         gy = self.gread(rec["y"])
-        w = self.m.P(p + ".conv.weight")
         gu = self.buf(n, 2 * hh, 2 * ww, c)
-        self.dgrad(p + ".conv.dgrad", gy, c, gu, c, [w], lambda: w, c, c, 3, conv=(n, 2 * hh, 2 * ww))
+        self.dx(rec["a"], gy, gu)
         dst, acc = self.gact(rec["x"])
-        self.prog.add(p + ".up_adj", self.lib.sgd_resample_bwd, _ptr(gu), n, hh, ww, c, L.RS_UP2, _ptr(dst), acc)
-        self.wgrad(p + ".conv", rec["a"], gy, c, c, c, 9, n * 4 * hh * ww, p + ".conv.weight", p + ".conv.bias")
+        self.prog.add(rec["p"] + ".up_adj", self.lib.sgd_resample_bwd, _ptr(gu), n, hh, ww, c, L.RS_UP2, _ptr(dst), acc)
+        self.dw(rec["a"], gy)
 
     def _attn_lr(self, rec):
-        """Attention_LR backward (autograd of crossattetion_lr.py:81-142).  With zero-padded heads (rec["pads"], head widths
-        the attention core has no instance for) every tensor between the projections is dp wide per head, the adjoint
-        operators are built from the padded weights and each padded weight gradient is gathered back into the parameter's
-        own shape (the padding rows / columns receive gradients that belong to no parameter)."""
-        n, p, ch, heads, d, T, J, ntok = (self.n, rec["p"], rec["ch"], rec["heads"], rec["d"], rec["T"], rec["J"],
-                                          rec["ntok"])
-        dp, pads = rec.get("dp", d), rec.get("pads")
-        P, lib = self.m.P, self.lib
+        """Attention_LR backward (autograd of crossattetion_lr.py:81-142).  With zero-padded heads (dp > d: head widths the
+        attention core has no instance for) every tensor between the projections is dp wide per head; dx / dw build the
+        adjoint operators from the padded weights and gather each padded weight gradient back into the parameter's shape."""
+        n, p, ch, heads, d, dp, T, J, ntok = (self.n, rec["p"], rec["ch"], rec["heads"], rec["d"], rec["dp"], rec["T"],
+                                              rec["J"], rec["ntok"])
         x, gy = rec["x"], self.gread(rec["y"])
         rows = n * T
         inner = heads * dp
-
-        def adj(w, key):                       # forward weight as the adjoint operator sees it
-            return (lambda: w) if pads is None else (lambda: pads[key].apply(w.detach().float()))
-
-        def wgrad(tag, fwd, g, cout, cin, nrows, wname, key, bias_name=None):
-            self.wgrad_padded(tag, fwd, g, cout, cin, nrows, wname, None if pads is None else pads[key], bias_name,
-                              None if pads is None else pads["vec"])
-
         # y = x + LN_out(o):  LN_out backward (gamma trainable, beta is a buffer)
         go = self.buf(n, T, ch)
         self.ln_bwd(p + ".to_out.1", rec["o"], gy, rows, ch, p + ".to_out.1.gamma", go, 0)
-        wo = P(p + ".to_out.0.weight")
         gatt = self.buf(n, T, inner)
-        self.dgrad(p + ".to_out.0.dgrad", go, ch, gatt, inner, [wo], adj(wo, "out"), ch, inner, 1, m=rows)
-        wgrad(p + ".to_out.0", rec["aout"], go, ch, inner, rows, p + ".to_out.0.weight", "out")
+        self.dx(rec["aout"], go, gatt)
+        self.dw(rec["aout"], go)
         # multi-query attention core
         q, kv = rec["q"], rec["kv"]
         gq, gkv = self.buf(n, T, inner), self.buf(n, J, 2 * dp)
@@ -614,33 +594,32 @@ class Backward:
                       _ptr(rec["lse"]), _ptr(dvec), n, heads, T, J, dp, d ** -0.5, _ptr(gq), _ptr(gkv),
                       C.c_void_p(gkv.data_ptr() + 4 * dp))
         # to_q / to_kv share LN(x): gradient of the normalised input is the sum of both adjoints
-        wq, wkv = P(p + ".to_q.weight"), P(p + ".to_kv.weight")
         gxn = self.buf(n, T, ch)
-        self.dgrad(p + ".to_q.dgrad", gq, inner, gxn, ch, [wq], adj(wq, "q"), inner, ch, 1, m=rows)
-        wgrad(p + ".to_q", rec["aq"], gq, inner, ch, rows, p + ".to_q.weight", "q")
+        self.dx(rec["aq"], gq, gxn)
+        self.dw(rec["aq"], gq)
         gkv_self = self.buf(n, T, 2 * dp)
         self.copy_op(p + ".gkv_self", gkv_self, gkv[:, ntok + 1:, :])
-        self.dgrad(p + ".to_kv.dgrad", gkv_self, 2 * dp, gxn, ch, [wkv], adj(wkv, "kv"), 2 * dp, ch, 1, m=rows, acc=True)
-        wgrad(p + ".to_kv", rec["akv"], gkv_self, 2 * dp, ch, rows, p + ".to_kv.weight", "kv")
+        self.dx(rec["akv"], gkv_self, gxn, acc=True)
+        self.dw(rec["akv"], gkv_self)
         # null key/value: summed over the batch
-        if pads is None:
-            self.colsum(p + ".null_kv", C.c_void_p(gkv.data_ptr() + 4 * ntok * 2 * d), n, 2 * d, J * 2 * d, p + ".null_kv")
+        gnull = C.c_void_p(gkv.data_ptr() + 4 * ntok * 2 * dp)
+        if rec["null_pad"] is None:
+            self.colsum(p + ".null_kv", gnull, n, 2 * dp, J * 2 * dp, p + ".null_kv")
         else:
             tn = self.buf(2, dp)
-            self.prog.add(p + ".null_kv", lib.sgd_colsum, C.c_void_p(gkv.data_ptr() + 4 * ntok * 2 * dp), n, 2 * dp,
-                          J * 2 * dp, _ptr(tn), 0, self.unscale, _ptr(self.cwork), self.CW)
-            self.gather_op(p + ".null_kv.unpad", p + ".null_kv", tn, pads["null"])
+            self.prog.add(p + ".null_kv", self.lib.sgd_colsum, gnull, n, 2 * dp, J * 2 * dp, _ptr(tn), 0, self.unscale,
+                          _ptr(self.cwork), self.CW)
+            self.gather_op(p + ".null_kv.unpad", p + ".null_kv", tn, rec["null_pad"])
         # context keys/values -> to_context.1 (Linear) -> to_context.0 (LayerNorm) -> shared context tokens
-        ctx = rec["ctx"]
+        context = rec["context"]
+        ctx = context.shape[-1]
         gckv = self.buf(n, ntok, 2 * dp)
         self.copy_op(p + ".gkv_ctx", gckv, gkv[:, :ntok, :])
-        wc = P(p + ".to_context.1.weight")
-        wgrad(p + ".to_context.1", rec["actx"], gckv, 2 * dp, ctx, n * ntok, p + ".to_context.1.weight", "kv",
-              p + ".to_context.1.bias")
+        self.dw(rec["actx"], gckv)
         gcn = self.buf(n, ntok, ctx)
-        self.dgrad(p + ".to_context.1.dgrad", gckv, 2 * dp, gcn, ctx, [wc], adj(wc, "kv"), 2 * dp, ctx, 1, m=n * ntok)
-        cdst, cacc = self.gact(rec["context"])
-        self.ln_bwd(p + ".to_context.0", rec["context"], gcn, n * ntok, ctx, p + ".to_context.0.weight", cdst, cacc,
+        self.dx(rec["actx"], gckv, gcn)
+        cdst, cacc = self.gact(context)
+        self.ln_bwd(p + ".to_context.0", context, gcn, n * ntok, ctx, p + ".to_context.0.weight", cdst, cacc,
                     beta_name=p + ".to_context.0.bias")
         # input LayerNorm (gamma trainable, beta buffer) + the residual path
         dst, acc = self.gact(x)
@@ -787,7 +766,7 @@ class Backward:
                     off += v.numel()
                 return t
             dw_dst, db_dst = span(wv, c1 - c0, ech), span(bv, c1 - c0, 1)
-        self.wgrad(tag, rec["a"], gsl, fw, c1 - c0, ech, 1, n, None, None, dw_view=dw_dst)
+        self.wgrad(tag, rec["a"].a, gsl, fw, c1 - c0, ech, 1, n, None, None, dw_view=dw_dst)
         self.prog.add(tag + ".bias", self.lib.sgd_colsum, _ptr(gsl), n, c1 - c0, fw, _ptr(db_dst), 0, self.unscale,
                       _ptr(self.cwork), self.CW)
         for i in range(i1 - 1, i0 - 1, -1):
@@ -795,44 +774,34 @@ class Backward:
             self.wrote(names[i] + ".emb_layers.1.bias")
 
     def _mlp2(self, rec):
-        """Linear -> SiLU -> Linear (time_embed / mlp_cond)"""
-        n, name = self.n, rec["name"]
-        P = self.m.P
+        """Linear -> SiLU -> Linear (time_embed / mlp_cond / to_time_tokens / cond_mlp); the first layer's input is no activation"""
         gy = self.gread(rec["y"])
-        cin, mid, cout = rec["cin"], rec["mid"], rec["cout"]
-        self.wgrad(name + ".2", rec["a2"], gy, cout, cout, mid, 1, n, name + ".2.weight", name + ".2.bias")
-        w2 = P(name + ".2.weight")
+        n, mid = rec["h"].shape
+        self.dw(rec["a2"], gy)
         gh_act = self.buf(n, mid)
-        self.dgrad(name + ".2.dgrad", gy, cout, gh_act, mid, [w2], lambda: w2, cout, mid, 1, m=n)
+        self.dx(rec["a2"], gy, gh_act)
         gh = self.buf(n, mid)
-        self.prog.add(name + ".silu_bwd", self.lib.sgd_silu_bwd, _ptr(rec["h"]), _ptr(gh_act), n * mid, _ptr(gh))
-        self.wgrad(name + ".0", rec["a0"], gh, mid, mid, cin, 1, n, name + ".0.weight", name + ".0.bias")
+        self.prog.add(rec["name"] + ".silu_bwd", self.lib.sgd_silu_bwd, _ptr(rec["h"]), _ptr(gh_act), n * mid, _ptr(gh))
+        self.dw(rec["a0"], gh)
 
     def _mlp_chain(self, rec):
         """to_cond_tokens_2d (openaimodel_ca.py:606-614): Linear -> SiLU -> Linear -> SiLU -> Linear -> SiLU -> Linear over
         the n*T token rows; every SiLU was the next GEMM's prologue, so each layer's input tensor is pre-activation"""
-        rows, P = rec["rows"], self.m.P
         g = self.gread(rec["y"])                          # [n, T*ctx] == [n*T, ctx] rows of the last layer's output
-        layers = rec["layers"]
-        for li in range(len(layers) - 1, -1, -1):
-            ly = layers[li]
-            name, cin, cout = ly["name"], ly["cin"], ly["cout"]
-            self.wgrad(name, ly["a"], g, cout, cout, cin, 1, rows, name + ".weight", name + ".bias")
+        for li, (x, layer) in reversed(list(enumerate(rec["layers"]))):
+            self.dw(layer, g)
             if li == 0:
                 break                                      # the layer input is the guidance itself: no gradient wanted
-            w = P(name + ".weight")
-            gact = self.buf(rows, cin)
-            self.dgrad(name + ".dgrad", g, cout, gact, cin, [w], lambda w=w: w, cout, cin, 1, m=rows)
-            gpre = self.buf(rows, cin)
-            self.prog.add(name + ".silu_bwd", self.lib.sgd_silu_bwd, _ptr(ly["x"]), _ptr(gact), rows * cin, _ptr(gpre))
+            gact, gpre = self.buf(*x.shape), self.buf(*x.shape)
+            self.dx(layer, g, gact)
+            self.prog.add(_tag(layer) + ".silu_bwd", self.lib.sgd_silu_bwd, _ptr(x), _ptr(gact), x.numel(), _ptr(gpre))
             g = gpre
 
     # ---------------------------------------------------------------- execution
     def run(self, geps_nchw):
         lib = self.lib
         stream = torch.cuda.current_stream().cuda_stream
-        if getattr(self, "_pack_batch", None) is None or len(self._pack_batch.packs) != len(self.packs):
-            from .unet import _PackBatch
+        if self._pack_batch is None or len(self._pack_batch.packs) != len(self.packs):
             self._pack_batch = _PackBatch(self.packs, self.prec, self.dev)
         self._pack_batch.refresh(stream)
         for a, pk in self.late:
@@ -899,7 +868,7 @@ class Backward:
         self._windows = (sum(inside), len(inside))
 
     def _own_flag(self):
-        if getattr(self, "_flag", None) is None:
+        if self._flag is None:
             self._flag = torch.zeros(1, dtype=torch.float32, device=self.dev)
         return self._flag
 

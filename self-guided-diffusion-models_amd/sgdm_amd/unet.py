@@ -12,6 +12,7 @@ implicit-GEMM convolution's loader/epilogue; attention cores as fused MFMA kerne
 for parameter storage, device memory and streams only.  There is no CPU / eager fallback: without the
 HIP library or a GPU the forward raises.
 """
+import collections
 import ctypes as C
 import weakref
 import math
@@ -173,6 +174,7 @@ class _Packed:
 
     def __init__(self, srcs, ksize, prec, pad=None, subpixel=False):
         self.srcs = srcs                     # list of parameters concatenated along dim 0
+        self.names = ()                      # their names (_Engine.pack)
         self.ksize = ksize
         self.prec = prec
         self.pad = pad                       # _Pad: the packed operator is the zero-padded re-layout of the parameter
@@ -246,7 +248,7 @@ class _FusedPacked:
     inference evaluation (the training forward launches the pair from their own packs)."""
 
     def __init__(self, w3, w1, b3, b1, prec):
-        self.srcs, self.prec = [w3, w1, b3, b1], prec
+        self.srcs, self.names, self.prec = [w3, w1, b3, b1], (), prec
         self.cout, self.cin, self.caux = w3.shape[0], w3.shape[1], w1.shape[1]
         assert w1.shape[0] == self.cout and prec != L.PREC_F32
         lib = L.load()
@@ -368,6 +370,13 @@ class _PackBatch:
                     AMAX_OF[p.data_ptr()] = (p._version, pk.amax, weakref.ref(p))
         for pk in self.packs:                                      # the rest, and small stale sets, one by one
             pk.refresh(stream)
+
+
+# One forward GEMM as the backward program needs it (train.Backward.dx / dw): the descriptor `a` (its geometry:
+# train.gemm_geometry), the pack `pk` (the weight parameters `srcs`, `ksize`, the zero-padding re-layout `pad`), the names of
+# the weight parameter(s) and of the bias parameter (None: no bias, or one that is no parameter's), and the bias's _Pad where
+# the launch reads a zero-padded copy of it (_Engine.padded).
+_Layer = collections.namedtuple("_Layer", "a pk wnames bias bias_pad")
 
 
 class _Program:
@@ -712,12 +721,13 @@ class _Engine:
 
     def pack(self, names, ksize, pad=None, subpixel=False):
         pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad, subpixel)
+        pk.names = tuple(names)
         self.packed.append(pk)
         return pk
 
     def up_conv(self, tag, x0, c0, y, cout, wname, conv, *, stats=False, **kw):
-        """nearest-x2-upsample 3x3 conv (conv[6] == RS_UP2).  Returns the DIRECT RS_UP2 descriptor: the tape describes the layer
-        as the conv it is, and the backward's weight gradient re-stages the upsampled input from it.  Where
+        """nearest-x2-upsample 3x3 conv (conv[6] == RS_UP2).  Returns the record of the DIRECT RS_UP2 descriptor: the tape
+        describes the layer as the conv it is, and the backward's weight gradient re-stages the upsampled input from it.  Where
         sgd_igemm_subpixel_ok allows (split modes, ...; SGDM_SUBPIXEL=0: never) the launch is the sub-pixel conv at the input
         resolution -- 4 taps per output instead of 9 -- on a pack of its own; the descriptor is then not launched."""
         assert conv[6] == L.RS_UP2
@@ -756,8 +766,17 @@ class _Engine:
         """stats=True: the epilogue also writes the GroupNorm statistics of y (consumed by gn() through
         sgd_stats_reduce instead of a sgd_chan_stats pass over the tensor).  y=None: the output pointer is set later
         (train_bufs; res_later: so is the residual's).  when: the program variant this launch belongs to (_Program.add).
-        aux=(x0, c0, x1, c1): the launch is sgd_igemm_fused_aux with this second input (pk: a _FusedPacked)."""
+        aux=(x0, c0, x1, c1): the launch is sgd_igemm_fused_aux with this second input (pk: a _FusedPacked).
+        bias: a parameter's name, (name, _Pad or None) for a parameter the launch reads as a zero-padded copy, or a tensor that
+        is no parameter.  Returns the layer's record (_Layer)."""
+        bias_name = bias_pad = None
+        if isinstance(bias, str):
+            bias = (bias, None)
+        if isinstance(bias, tuple):
+            bias_name, bias_pad = bias
+            bias = self.m.P(bias_name) if bias_pad is None else self.padded(bias_name, bias_pad)
         a = L.IgemmArgs()
+        layer = _Layer(a, pk, pk.names, bias_name, bias_pad)
         a.x0, a.x1, a.c0, a.c1 = x0.data_ptr(), (x1.data_ptr() if x1 is not None else 0), c0, c1
         rows_n = conv[0] if conv is not None else (m // rows_per_n if rows_per_n else 0)
         if conv is not None:
@@ -819,7 +838,7 @@ class _Engine:
             nbytes += 4.0 * (rows * (ac0 + ac1) + (ac0 + ac1) * cout)
             self.prog.keep.append(xa)
             self.prog.add(tag, self.lib.sgd_igemm_fused_aux, C.byref(a), C.byref(xa), flops=flops, nbytes=nbytes, when=when)
-            return a
+            return layer
         if narrow:
             wsrc, fn = pk.srcs[0], self.lib.sgd_conv3_narrow_in
             x_p, b_p, y_p, s_p = _ptr(x0), C.c_void_p(a.bias or 0), C.c_void_p(a.y), C.c_void_p(a.stats or 0)
@@ -848,7 +867,7 @@ class _Engine:
             self.prog.add(tag, sgd_conv3_narrow_out, flops=flops, nbytes=nbytes)
         elif launch:        # launch=False: descriptor only (the backward's weight gradient reads it)
             self.prog.add(tag, self.lib.sgd_igemm, C.byref(a), flops=flops, nbytes=nbytes, when=when)
-        return a
+        return layer
 
     def gn(self, tag, srcs, hw, gname, film=None, film_ld=0, eps=GN_EPS):
         """srcs: list of (tensor, channels) forming a virtual concat -> (a, b) coefficient buffers"""
@@ -898,11 +917,10 @@ class _Engine:
         emb = self.buf(n, ted)
         e1 = self.buf(n, ted)
         a0 = self.igemm("time_embed.0", self.temb, mc, e1, ted, self.pack(["time_embed.0.weight"], 1), m=n,
-                        bias=P("time_embed.0.bias"))
+                        bias="time_embed.0.bias")
         a2 = self.igemm("time_embed.2", e1, ted, emb, ted, self.pack(["time_embed.2.weight"], 1), m=n, silu=1,
-                        bias=P("time_embed.2.bias"))
-        self.tape.append(dict(kind="mlp2", name="time_embed", x=self.temb, h=e1, y=emb, a0=a0, a2=a2, cin=mc,
-                              mid=ted, cout=ted, add_to_y=False))
+                        bias="time_embed.2.bias")
+        self.tape.append(dict(kind="mlp2", name="time_embed", x=self.temb, h=e1, y=emb, a0=a0, a2=a2))
         self.context = None
         self.emb_c = None
         m._build_cond_path(self, emb)
@@ -939,7 +957,7 @@ class _Engine:
         t, c, hh, ww = cur
         a, b = self.gn("out.0", [(t, c)], hh * ww, "out.0")
         if self.head is None:
-            oc, hpk, hbias = m.out_channels, self.pack(["out.2.weight"], 3), P("out.2.bias")
+            oc, hpk, hbias = m.out_channels, self.pack(["out.2.weight"], 3), "out.2.bias"
         else:
             # rows [0, head) of the head conv: contiguous views of the two parameters (same storage and version counter, so
             # the pack follows the parameter like any other)
@@ -950,7 +968,7 @@ class _Engine:
         ah = self.igemm("out.2", t, c, self.eps_nhwc, oc, hpk,
                         conv=(n, hh, ww, hh, ww, 1, L.RS_NONE), pro=L.PRO_AFFINE_NC, silu=1, pa=a, pb=b,
                         bias=hbias)
-        self.tape.append(dict(kind="head", x=t, c=c, hw=(hh, ww), a=a, b=b, sums=self._last_sums, conv=ah))
+        self.tape.append(dict(kind="head", x=t, a=a, b=b, sums=self._last_sums, conv=ah))
 
     def _block(self, prefix, blk, srcs):
         """srcs: list of (tensor, C, H, W) (two entries = virtual concat [h, skip])"""
@@ -961,8 +979,8 @@ class _Engine:
                 (t, c, hh, ww), = srcs
                 y = self.buf(self.n, hh, ww, layer[2])
                 a = self.igemm(p, t, c, y, layer[2], self.pack([p + ".weight"], 3),
-                               conv=(self.n, hh, ww, hh, ww, 1, L.RS_NONE), bias=self.m.P(p + ".bias"), stats=True)
-                self.tape.append(dict(kind="conv_in", p=p, x=t, y=y, a=a, cin=c, cout=layer[2], hw=(hh, ww)))
+                               conv=(self.n, hh, ww, hh, ww, 1, L.RS_NONE), bias=p + ".bias", stats=True)
+                self.tape.append(dict(kind="conv_in", p=p, x=t, y=y, a=a))
                 srcs = [(y, layer[2], hh, ww)]
             elif kind == "res":
                 srcs = [self._res(p, layer, srcs)]
@@ -972,16 +990,16 @@ class _Engine:
                 (t, c, hh, ww), = srcs
                 y = self.buf(self.n, hh // 2, ww // 2, c)
                 a = self.igemm(p + ".op", t, c, y, c, self.pack([p + ".op.weight"], 3),
-                               conv=(self.n, hh, ww, hh // 2, ww // 2, 2, L.RS_NONE), bias=self.m.P(p + ".op.bias"),
+                               conv=(self.n, hh, ww, hh // 2, ww // 2, 2, L.RS_NONE), bias=p + ".op.bias",
                                stats=True)
-                self.tape.append(dict(kind="down", p=p, x=t, y=y, c=c, hw_in=(hh, ww), a=a))
+                self.tape.append(dict(kind="down", p=p, x=t, y=y, a=a))
                 srcs = [(y, c, hh // 2, ww // 2)]
             elif kind == "up":
                 (t, c, hh, ww), = srcs
                 y = self.buf(self.n, hh * 2, ww * 2, c)
                 a = self.up_conv(p + ".conv", t, c, y, c, p + ".conv.weight",
-                                 (self.n, hh, ww, hh * 2, ww * 2, 1, L.RS_UP2), bias=self.m.P(p + ".conv.bias"), stats=True)
-                self.tape.append(dict(kind="up", p=p, x=t, y=y, c=c, hw_in=(hh, ww), a=a))
+                                 (self.n, hh, ww, hh * 2, ww * 2, 1, L.RS_UP2), bias=p + ".conv.bias", stats=True)
+                self.tape.append(dict(kind="up", p=p, x=t, y=y, a=a))
                 srcs = [(y, c, hh * 2, ww * 2)]
         return srcs[0]
 
@@ -1001,7 +1019,7 @@ class _Engine:
                          p + ".in_layers.0")
         sums1 = self._last_sums
         h1 = self.buf(n, ho, wo, cout)
-        kw1 = dict(x1=t1, c1=c1, pro=L.PRO_AFFINE_NC, silu=1, pa=a1, pb=b1, bias=P(p + ".in_layers.2.bias"), stats=ss)
+        kw1 = dict(x1=t1, c1=c1, pro=L.PRO_AFFINE_NC, silu=1, pa=a1, pb=b1, bias=p + ".in_layers.2.bias", stats=ss)
         if rs == L.RS_UP2:
             ac1 = self.up_conv(p + ".in_layers.2", t0, c0, h1, cout, p + ".in_layers.2.weight", (n, hh, ww, ho, wo, 1, rs), **kw1)
         else:
@@ -1025,7 +1043,7 @@ class _Engine:
             skip = None if fuse else self.buf(n, hh, ww, cout)     # (fused: allocated by the first training forward)
             pks = self.pack([p + ".skip_connection.weight"], 1)
             ask = self.igemm(p + ".skip_connection", t0, c0, skip, cout, pks, x1=t1, c1=c1, m=n * hh * ww,
-                             bias=P(p + ".skip_connection.bias"), when=pair)
+                             bias=p + ".skip_connection.bias", when=pair)
             res, res_mode = skip, L.RS_NONE
         else:
             assert t1 is None
@@ -1033,21 +1051,21 @@ class _Engine:
         y = self.buf(n, ho, wo, cout)
         pk2 = self.pack([p + ".out_layers.3.weight"], 3)
         ac2 = self.igemm(p + ".out_layers.3", h1, cout, y, cout, pk2,
-                         bias=P(p + ".out_layers.3.bias"), res=res, res_mode=res_mode, when=pair, res_later=fuse, **kw2)
+                         bias=p + ".out_layers.3.bias", res=res, res_mode=res_mode, when=pair, res_later=fuse, **kw2)
         if fuse:
             # y = conv3x3(act(h1)) + conv1x1(x) + b3 + bs as ONE GEMM over K = 9 cout + cin (sgd_igemm_fused_aux): no skip tensor
             # written and read back, eleven launches fewer per evaluation of the flagship model
-            self.train_bufs.append(((n, hh, ww, cout), [(ask, "y"), (ac2, "res")]))
+            self.train_bufs.append(((n, hh, ww, cout), [(ask.a, "y"), (ac2.a, "res")]))
             fpk = _FusedPacked(P(p + ".out_layers.3.weight"), P(p + ".skip_connection.weight"), P(p + ".out_layers.3.bias"),
                                P(p + ".skip_connection.bias"), self.prec)
             self.fused_packs.append(fpk)
             self.train_packs += [pks, pk2]
             self.igemm(p + ".out_layers.3", h1, cout, y, cout, fpk, bias=fpk.bias, when="infer", aux=(t0, c0, t1, c1), **kw2)
         pbox, sbox = C.c_float(0.0), C.c_uint32(0)
-        self.drops.append((ac2, pbox, sbox))                  # nn.Dropout sits in front of conv2 (openaimodel.py:272)
+        self.drops.append((ac2.a, pbox, sbox))                # nn.Dropout sits in front of conv2 (openaimodel.py:272)
         self.tape.append(dict(kind="res", drop_p=pbox, drop_seed=sbox, p=p,
-                              srcs=[(t0, c0)] + ([(t1, c1)] if t1 is not None else []), cin=cin,
-                              cout=cout, hw_in=(hh, ww), hw_out=(ho, wo), rs=rs, a1=a1, b1=b1, sums1=sums1, h1=h1,
+                              srcs=[(t0, c0)] + ([(t1, c1)] if t1 is not None else []),
+                              hw_in=(hh, ww), rs=rs, a1=a1, b1=b1, sums1=sums1, h1=h1,
                               a2=a2, b2=b2, sums2=sums2, film_off=self.film_off[p], conv1=ac1, conv2=ac2, skip=ask,
                               y=y, ss=ss))
         return (y, cout, ho, wo)
@@ -1350,7 +1368,7 @@ class UNetModel(UNetModelBase):
         a, b = eng.gn(p + ".norm", [(t, c)], T, p + ".norm", eps=1e-6)
         x = eng.buf(n, T, inner)
         eng.igemm(p + ".proj_in", t, c, x, inner, eng.pack([p + ".proj_in.weight"], 1), m=rows, rows_per_n=T,
-                  pro=L.PRO_AFFINE_NC, pa=a, pb=b, bias=P(p + ".proj_in.bias"))
+                  pro=L.PRO_AFFINE_NC, pa=a, pb=b, bias=p + ".proj_in.bias")
         for i in range(self.transformer_depth):
             blk = f"{p}.transformer_blocks.{i}"
             for att, nrm in ((".attn1", ".norm1"), (".attn2", ".norm2")):
@@ -1367,23 +1385,23 @@ class UNetModel(UNetModelBase):
                              n, heads, T, T, d, d ** -0.5, _ptr(o), inner, _ptr(lse))
                 xn = eng.buf(n, T, inner)
                 eng.igemm(blk + att + ".to_out.0", o, inner, xn, inner, eng.pack([blk + att + ".to_out.0.weight"], 1), m=rows,
-                          bias=P(blk + att + ".to_out.0.bias"), res=x)
+                          bias=blk + att + ".to_out.0.bias", res=x)
                 x = xn
             st = eng.buf(rows, 2)
             eng.prog.add(blk + ".norm3", lib.sgd_ln_stats, _ptr(x), rows, inner, LN_EPS, _ptr(st))
             hid = eng.buf(rows, 8 * inner)
             eng.igemm(blk + ".ff.net.0.proj", x, inner, hid, 8 * inner, eng.pack([blk + ".ff.net.0.proj.weight"], 1), m=rows,
                       pro=L.PRO_LN_ROW, pa=st, pb=P(blk + ".norm3.weight"), pc=P(blk + ".norm3.bias"),
-                      bias=P(blk + ".ff.net.0.proj.bias"))
+                      bias=blk + ".ff.net.0.proj.bias")
             gated = eng.buf(rows, 4 * inner)
             eng.prog.add(blk + ".ff.geglu", lib.sgd_geglu, _ptr(hid), rows, 4 * inner, _ptr(gated))
             xn = eng.buf(n, T, inner)
             eng.igemm(blk + ".ff.net.2", gated, 4 * inner, xn, inner, eng.pack([blk + ".ff.net.2.weight"], 1), m=rows,
-                      bias=P(blk + ".ff.net.2.bias"), res=x)
+                      bias=blk + ".ff.net.2.bias", res=x)
             x = xn
         y = eng.buf(n, hh, ww, ch)
         eng.igemm(p + ".proj_out", x, inner, y, ch, eng.pack([p + ".proj_out.weight"], 1), m=rows, rows_per_n=T,
-                  bias=P(p + ".proj_out.bias"), res=t, stats=True)
+                  bias=p + ".proj_out.bias", res=t, stats=True)
         return (y, ch, hh, ww)
 
     def _res_prefixes(self):
@@ -1398,7 +1416,7 @@ class UNetModel(UNetModelBase):
         eng.emb_c = eng.buf(eng.n, ted // 2)                                      # emb = cat(time, cond), :942
         skinny = self.cond_dim >= 1024 and eng.n <= 256          # cluster k = 5000: split the long reduction over blocks
         a0 = eng.igemm("mlp_cond.0", eng.cond_m, self.cond_dim, c1, ted // 2, eng.pack(["mlp_cond.0.weight"], 1),
-                       m=eng.n, bias=P("mlp_cond.0.bias"), launch=not skinny)
+                       m=eng.n, bias="mlp_cond.0.bias", launch=not skinny)
         if skinny:
             ksplit = max(1, min(64, self.cond_dim // 128))
             work = eng.buf(ksplit, eng.n, ted // 2)
@@ -1440,9 +1458,8 @@ class UNetModel(UNetModelBase):
             eng.prog.add("mlp_cond.0", mlp_cond0, flops=2.0 * n * K * nout, nbytes=4.0 * (n * K + K * nout + n * nout))
             eng.prog.keep.append((wt, bs))
         a2 = eng.igemm("mlp_cond.2", c1, ted // 2, eng.emb_c, ted // 2, eng.pack(["mlp_cond.2.weight"], 1), m=eng.n,
-                       silu=1, bias=P("mlp_cond.2.bias"))
-        eng.tape.append(dict(kind="mlp2", name="mlp_cond", x=eng.cond_m, h=c1, y=eng.emb_c, a0=a0, a2=a2,
-                             cin=self.cond_dim, mid=ted // 2, cout=ted // 2, add_to_y=False))
+                       silu=1, bias="mlp_cond.2.bias")
+        eng.tape.append(dict(kind="mlp2", name="mlp_cond", x=eng.cond_m, h=c1, y=eng.emb_c, a0=a0, a2=a2))
 
     def _build_attn(self, eng, p, layer, src):
         """AttentionBlock + QKVAttentionLegacy (openaimodel.py:365-371, 403-420)"""
@@ -1450,7 +1467,7 @@ class UNetModel(UNetModelBase):
             return self._build_st(eng, p, layer, src)
         _, ch, heads = layer
         t, c, hh, ww = src
-        n, T, P = eng.n, hh * ww, self.P
+        n, T = eng.n, hh * ww
         d = ch // heads
         # head widths the attention core has no instance for (config/dynamic/unet.yaml: 256 / 32 = 8 channels per head at ds 2) run
         # zero-padded to dp, like Attention_LR's: qkv's packed weight / bias and proj_out's packed weight are padded re-layouts of
@@ -1472,9 +1489,8 @@ class UNetModel(UNetModelBase):
         a, b = eng.gn(p + ".norm", [(t, c)], T, p + ".norm")
         sums = eng._last_sums
         qkv = eng.buf(n, T, 3 * inner)
-        qbias = eng.padded(p + ".qkv.bias", pads["qkv_bias"]) if pads else P(p + ".qkv.bias")
         aq = eng.igemm(p + ".qkv", t, c, qkv, 3 * inner, eng.pack([p + ".qkv.weight"], 1, pad("qkv")), m=n * T, rows_per_n=T,
-                       pro=L.PRO_AFFINE_NC, pa=a, pb=b, bias=qbias)
+                       pro=L.PRO_AFFINE_NC, pa=a, pb=b, bias=(p + ".qkv.bias", pad("qkv_bias")))
         att = eng.buf(n, T, inner)
         lse = eng.buf(n, heads, T)                         # softmax statistics kept for the backward
         # head stride, k / v offsets of the (padded) layout; scale = (d^-1/4)^2 applied to q.k
@@ -1484,8 +1500,8 @@ class UNetModel(UNetModelBase):
                      n, heads, T, T, dp, 1.0 / math.sqrt(d), _ptr(att), inner, _ptr(lse))
         y = eng.buf(n, hh, ww, ch)
         ap = eng.igemm(p + ".proj_out", att, inner, y, ch, eng.pack([p + ".proj_out.weight"], 1, pad("out")), m=n * T,
-                       rows_per_n=T, bias=P(p + ".proj_out.bias"), res=t, stats=True)
-        eng.tape.append(dict(kind="attn", p=p, x=t, ch=ch, heads=heads, d=d, dp=dp, pads=pads, T=T, hw=(hh, ww), a=a, b=b,
+                       rows_per_n=T, bias=p + ".proj_out.bias", res=t, stats=True)
+        eng.tape.append(dict(kind="attn", p=p, x=t, ch=ch, heads=heads, d=d, dp=dp, T=T, hw=(hh, ww), a=a, b=b,
                              sums=sums, qkv=qkv, att=att, lse=lse, qkv_args=aq, proj_args=ap, y=y, qkv_layout=(hs, ko, vo)))
         return (y, ch, hh, ww)
 
@@ -1605,24 +1621,21 @@ class UNetModelCA(UNetModelBase):
         raw_t, raw_c = raw2[:, :wt], raw2[:, wt:]           # strided views: keys of the token gradients
         t1 = eng.buf(n, mc)
         a0 = eng.igemm("to_time_tokens.0", eng.temb, mc, t1, mc, eng.pack(["to_time_tokens.0.weight"], 1), m=n,
-                       bias=P("to_time_tokens.0.bias"))
+                       bias="to_time_tokens.0.bias")
         a2 = eng.igemm("to_time_tokens.2", t1, mc, raw, wt, eng.pack(["to_time_tokens.2.weight"], 1),
-                       m=n, silu=1, bias=P("to_time_tokens.2.bias"), y_ld=ntok * ctx)
-        eng.tape.append(dict(kind="mlp2", name="to_time_tokens", x=eng.temb, h=t1, y=raw_t, a0=a0, a2=a2, cin=mc,
-                             mid=mc, cout=wt, add_to_y=False))
+                       m=n, silu=1, bias="to_time_tokens.2.bias", y_ld=ntok * ctx)
+        eng.tape.append(dict(kind="mlp2", name="to_time_tokens", x=eng.temb, h=t1, y=raw_t, a0=a0, a2=a2))
         if self.cond_token_num == 1:
             al = eng.igemm("to_cond_tokens.0", eng.cond_m, self.cond_dim, raw, ctx * NUM_COND_TOKENS,
-                           eng.pack(["to_cond_tokens.0.weight"], 1), m=n, bias=P("to_cond_tokens.0.bias"),
+                           eng.pack(["to_cond_tokens.0.weight"], 1), m=n, bias="to_cond_tokens.0.bias",
                            y_ld=ntok * ctx, y_off=wt)
-            eng.tape.append(dict(kind="linear", name="to_cond_tokens.0", y=raw_c, a=al, cin=self.cond_dim,
-                                 cout=ctx * NUM_COND_TOKENS))
+            eng.tape.append(dict(kind="linear", y=raw_c, a=al))
             c1 = eng.buf(n, ted)
             b0 = eng.igemm("cond_mlp.0", eng.cond_m, self.cond_dim, c1, ted, eng.pack(["cond_mlp.0.weight"], 1), m=n,
-                           bias=P("cond_mlp.0.bias"))
+                           bias="cond_mlp.0.bias")
             b2 = eng.igemm("cond_mlp.2", c1, ted, emb, ted, eng.pack(["cond_mlp.2.weight"], 1), m=n, silu=1,
-                           bias=P("cond_mlp.2.bias"), res=emb)                    # emb = emb + cond_condensed, :977
-            eng.tape.append(dict(kind="mlp2", name="cond_mlp", x=eng.cond_m, h=c1, y=emb, a0=b0, a2=b2,
-                                 cin=self.cond_dim, mid=ted, cout=ted, add_to_y=True))
+                           bias="cond_mlp.2.bias", res=emb)                    # emb = emb + cond_condensed, :977
+            eng.tape.append(dict(kind="mlp2", name="cond_mlp", x=eng.cond_m, h=c1, y=emb, a0=b0, a2=b2))
         if T > 1:
             # token guidance (openaimodel_ca.py:987-1013): cond [n, T, cd] -> per-token MLP to_cond_tokens_2d -> T context
             # tokens behind the 8 time tokens; emb += cond_mlp(pooled token)
@@ -1636,20 +1649,19 @@ class UNetModelCA(UNetModelBase):
                 last = idx == 6
                 dst = raw if last else eng.buf(rows, wout)
                 al = eng.igemm(name, src, width, dst, wout, eng.pack([name + ".weight"], 1), m=rows, silu=int(li > 0),
-                               bias=P(name + ".bias"), orows=(T, ntok, NUM_TIME_TOKENS) if last else (0, 0, 0))
-                layers.append(dict(name=name, x=src, cin=width, cout=wout, a=al))
+                               bias=name + ".bias", orows=(T, ntok, NUM_TIME_TOKENS) if last else (0, 0, 0))
+                layers.append((src, al))                   # (pre-activation input, layer)
                 src, width = dst, wout
-            eng.tape.append(dict(kind="mlp_chain", layers=layers, y=raw_c, rows=rows))
+            eng.tape.append(dict(kind="mlp_chain", layers=layers, y=raw_c))
             pooled = eng.buf(n, cd)
             eng.prog.add("cond_pooled", eng.lib.sgd_token_pool, _ptr(eng.cond_m), n, T, cd,
                          1 if self.use_cls_token_as_pooled == True else 0, _ptr(pooled))     # noqa: E712  (reference: == True)
             c1 = eng.buf(n, ted)
             b0 = eng.igemm("cond_mlp.0", pooled, cd, c1, ted, eng.pack(["cond_mlp.0.weight"], 1), m=n,
-                           bias=P("cond_mlp.0.bias"))
+                           bias="cond_mlp.0.bias")
             b2 = eng.igemm("cond_mlp.2", c1, ted, emb, ted, eng.pack(["cond_mlp.2.weight"], 1), m=n, silu=1,
-                           bias=P("cond_mlp.2.bias"), res=emb)
-            eng.tape.append(dict(kind="mlp2", name="cond_mlp", x=pooled, h=c1, y=emb, a0=b0, a2=b2, cin=cd, mid=ted,
-                                 cout=ted, add_to_y=True))
+                           bias="cond_mlp.2.bias", res=emb)
+            eng.tape.append(dict(kind="mlp2", name="cond_mlp", x=pooled, h=c1, y=emb, a0=b0, a2=b2))
             eng.token_guidance = True
         context = eng.buf(n, ntok, ctx)
         eng.prog.add("norm_cond", eng.lib.sgd_ln_apply, _ptr(raw), _ptr(P("norm_cond.weight")),
@@ -1690,11 +1702,10 @@ class UNetModelCA(UNetModelBase):
         cst = eng.buf(n * ntok, 2)
         eng.prog.add(p + ".to_context.0", lib.sgd_ln_stats, _ptr(eng.context), n * ntok, self.context_dim, LN_EPS,
                      _ptr(cst))
-        cbias = eng.padded(p + ".to_context.1.bias", pads["vec"]) if pads else P(p + ".to_context.1.bias")
         actx = eng.igemm(p + ".to_context.1", eng.context, self.context_dim, kv, 2 * dp,
                          eng.pack([p + ".to_context.1.weight"], 1, pad("kv")), m=n * ntok, pro=L.PRO_LN_ROW, pa=cst,
                          pb=P(p + ".to_context.0.weight"), pc=P(p + ".to_context.0.bias"),
-                         bias=cbias, orows=(ntok, J, 0))
+                         bias=(p + ".to_context.1.bias", pad("vec")), orows=(ntok, J, 0))
         null_kv = eng.padded(p + ".null_kv", pads["null"]) if pads else P(p + ".null_kv")
         eng.prog.add(p + ".null_kv", lib.sgd_fill_null_kv, _ptr(null_kv), n, J, ntok, dp, _ptr(kv))
         att = eng.buf(n, T, heads * dp)
@@ -1708,9 +1719,9 @@ class UNetModelCA(UNetModelBase):
         y = eng.buf(n, hh, ww, ch)
         eng.prog.add(p + ".to_out.1", lib.sgd_ln_apply, _ptr(o), _ptr(P(p + ".to_out.1.gamma")),
                      _ptr(P(p + ".to_out.1.beta")), _ptr(t), n * T, ch, LN_EPS, _ptr(y))
-        eng.tape.append(dict(kind="attn_lr", p=p, x=t, ch=ch, heads=heads, d=d, dp=dp, pads=pads, T=T, J=J, ntok=ntok,
-                             hw=(hh, ww), q=q, kv=kv, att=att, lse=lse, o=o, aq=aq, akv=akv, actx=actx, aout=aout, y=y,
-                             context=eng.context, ctx=self.context_dim))
+        eng.tape.append(dict(kind="attn_lr", p=p, x=t, ch=ch, heads=heads, d=d, dp=dp, null_pad=pad("null"), T=T, J=J,
+                             ntok=ntok, q=q, kv=kv, att=att, lse=lse, o=o, aq=aq, akv=akv, actx=actx, aout=aout, y=y,
+                             context=eng.context))
         return (y, ch, hh, ww)
 
     # ---- reference entry points (openaimodel_ca.py:879-1033)
