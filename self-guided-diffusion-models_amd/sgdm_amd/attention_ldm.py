@@ -23,7 +23,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .unet import LN_EPS, _Packed, _Pad, _ptr, default_precision, padded_head_dim
+from .packs import Packed, _Pad, _ptr
+from .train import wgrad_ksplit
+from .unet import LN_EPS, default_precision, padded_head_dim
 
 COLSUM_CHUNKS = 256          # row chunks of sgd_colsum's two-stage reduction
 
@@ -88,7 +90,7 @@ class CrossAttention(nn.Module):
     def _pack(self, key, param, prec, pad):
         pk = self._packs.get((key, prec))
         if pk is None:
-            pk = self._packs[(key, prec)] = _Packed([param], 1, prec, pad)
+            pk = self._packs[(key, prec)] = Packed([param], 1, prec, pad=pad)
         pk.refresh(torch.cuda.current_stream().cuda_stream)
         return pk
 
@@ -184,8 +186,7 @@ class CrossAttention(nn.Module):
     # ---- backward (exact fp32; see the module docstring)
     def _dgrad(self, lib, st, g, w_fwd, param, cout_fwd, cin_fwd, rows, out=None):
         """out (+)= g [rows, cout_fwd] . w_fwd [cout_fwd, cin_fwd]: the forward kernel on the adjoint-packed weight"""
-        from .train import _PackedAdj
-        pk = _PackedAdj([param], lambda: w_fwd, cout_fwd, cin_fwd, 1, L.PREC_F32, g.device)
+        pk = Packed([param], 1, L.PREC_F32, L.PACK_DGRAD, src_fn=lambda: w_fwd, dims=(cout_fwd, cin_fwd), device=g.device)
         pk.refresh(st)
         acc = out is not None
         y = out if acc else torch.empty(rows, cin_fwd, device=g.device)
@@ -200,7 +201,6 @@ class CrossAttention(nn.Module):
 
     def _wgrad(self, lib, st, xin, cin, ln, g, cout, rows):
         """dW [cout, cin] = g^T . act(xin) with act = the forward launch's LayerNorm-row prologue (or none)"""
-        from .train import wgrad_ksplit
         a = L.IgemmArgs()
         a.x0, a.c0, a.mode, a.m, a.stride, a.prec = xin.data_ptr(), cin, L.MODE_FLAT, rows, 1, L.PREC_F32
         if ln is not None:

@@ -31,7 +31,7 @@ import math
 import torch
 
 from . import _lib as L
-from .unet import _ptr
+from .unet import UNetModelBase, _ptr
 
 
 class _MSEFn(torch.autograd.Function):
@@ -233,7 +233,6 @@ def distill_teacher_from(model, ema=None, hip_precision=None):
     (``hip_precision``).  The inference-only modes 'f16' / 'bf16' are allowed: the teacher only ever runs under
     torch.no_grad().  Hand the result to ``LatentDiffusion.set_distill_teacher``."""
     import copy
-    from .unet import UNetModelBase
     if not isinstance(model, UNetModelBase):
         raise TypeError(f"distill_teacher_from copies a drop-in UNet, not {type(model).__name__}")
     if hip_precision is not None and hip_precision not in L.PREC_BY_NAME:
@@ -260,7 +259,6 @@ def _distill_setup(diff, student, kwargs, device):
     out_channels that differ; teacher and student the same object; a teacher that is in train mode or has parameters that
     require grad; a caller's cond_drop_mask (the student is trained on its conditional branch alone); distill_rescale off
     the fused path (the rescale needs both halves of the teacher's doubled evaluation)."""
-    from .unet import UNetModelBase
     # (progressive_steps without distill_guidance: w is None -- the teacher is evaluated once, conditionally, not guided)
     w, phi = diff.distill if diff.distill is not None else (None, 0.0)
     teacher = getattr(diff, "_distill_teacher", None)
@@ -517,12 +515,22 @@ def per_sample_loss(path, kind, diff, model_output, target, teach, dev, x_start,
     return per * weights[t], per.detach(), None     # the same weights on the torch chain
 
 
+def refuse_inference_only(model):
+    """the single-product modes (hip_precision 'f16' / 'bf16') have no backward: half-precision training needs loss-scale and
+    master-weight decisions this library has not made.  Raises before anything is launched."""
+    mods = model.modules() if isinstance(model, torch.nn.Module) else ()
+    for mod in mods:
+        name = getattr(mod, "hip_precision", None)
+        if name in L.INFERENCE_ONLY:
+            raise ValueError(f"hip_precision='{name}' is inference only (operands rounded once to 16 bits, no backward): "
+                             f"train with 'f32', 'f16x3' or 'bf16x3', or run this model under torch.no_grad() / eval()")
+
+
 def p_losses_hip(diff, x_start, t, noise=None, *args, **kwargs):
     """LatentDiffusion.p_losses (ddpm.py:54-86)"""
     # ---- 1. what is refused, all of it before the first launch
     fn = getattr(diff.denoise_fn, "__self__", diff.denoise_fn)        # the UNet (a bound forward or the module itself)
     if torch.is_grad_enabled() and isinstance(fn, torch.nn.Module) and fn.training and any(p.requires_grad for p in fn.parameters()):
-        from .train import refuse_inference_only
         refuse_inference_only(fn)                                         # a training step
     L.load()
     s, h = diff.sampler, diff.hparams

@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .unet import grad_health
 
 CHUNK = 4096
 
@@ -98,14 +99,13 @@ class FusedAdamWEma(torch.optim.Optimizer):
             # gate (ABI 18): the device's gradient-health flag -- the launch writes nothing while it is up, so gradients a
             # balanced-tail time-out poisoned never reach parameters, moments or EMA shadows (train.Backward.run raises it,
             # the engine's next poll_health() raises on the host and clears it)
-            from .unet import grad_health
             L.check(lib.sgd_adamw_ema_step(C.c_void_p(table.data_ptr()), C.c_void_p(cstart.data_ptr()), len(rows), total,
                                            float(group["lr"]), 1.0 - b1, b2, 1.0 - b2, group["eps"], group["weight_decay"],
                                            1.0 - b1 ** t, 1.0 - b2 ** t, omd, C.c_void_p(grad_health(dev).data_ptr()),
                                            torch.cuda.current_stream().cuda_stream), "sgd_adamw_ema_step")
             self._table_keep = (table, keep)
             # The kernel writes the parameters through raw pointers, which autograd's version counters do not see.
-            # Consumers that cache derived copies keyed on (data_ptr, _version) -- the UNet's igemm-packed forward and
-            # adjoint weights (unet._Packed, train._PackedAdj) and the FiLM bias concat -- must observe the update.
+            # Every derived copy (packs.Stale: the igemm-packed forward and adjoint weights, the FiLM bias concat, ...) follows
+            # the parameters' version counters and must observe the update.
             torch._C._increment_version(touched)
         return loss

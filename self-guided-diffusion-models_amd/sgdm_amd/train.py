@@ -46,8 +46,9 @@ from . import _lib as L
 from .losses import distill_teacher_from  # noqa: F401  (sgdm_amd.train.distill_teacher_from: INTEGRATION.md)
 # the names callers took from this module while the loss code lived here keep resolving; new code imports them from losses.py
 from .losses import (_LOSS_KIND, _LOSS_PAR, _MSEFn, _lv_tables, lv_decoder_bits, lv_kl_bits, lv_loss, lv_terms,  # noqa: F401
-                     lv_vlb_torch, p_losses_hip, simple_loss_torch as _simple_torch)
-from .unet import GN_EPS, GN_GROUPS, _PackBatch, _Program, _ptr
+                     lv_vlb_torch, p_losses_hip, refuse_inference_only, simple_loss_torch as _simple_torch)
+from .packs import Derived, PackBatch, Packed, _ptr
+from .unet import GN_EPS, GN_GROUPS, _Program, grad_health
 
 
 def progressive_next_stage(diff, ema=None, hip_precision=None):
@@ -74,57 +75,6 @@ def progressive_next_stage(diff, ema=None, hip_precision=None):
     diff.__dict__.pop("_pd_rows", None)
     diff.set_distill_teacher(teacher)                   # (drops the teacher runner)
     return K // 2
-
-
-class _PackedAdj:
-    """adjoint-packed weight (dgrad operator) of one forward weight, refreshed on version change.
-    ``src_fn`` returns the forward weight [cout_fwd, cin_fwd(, k, k)] (may be a slice/cat of parameters)."""
-
-    def __init__(self, deps, src_fn, cout_fwd, cin_fwd, ksize, prec, device):
-        self.deps, self.src_fn, self.ksize, self.prec = deps, src_fn, ksize, prec
-        self.cout_fwd, self.cin_fwd = cout_fwd, cin_fwd
-        lib = L.load()
-        nbytes = lib.sgd_packed_weight_bytes(cin_fwd, cout_fwd, ksize, prec)       # adjoint: outputs = cin_fwd
-        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-        self.cin_p = self.cout_p = 0
-        self.sig = None
-        self.scaled = prec != L.PREC_F32           # per-tensor power-of-two scale, as unet._Packed
-        if self.scaled:
-            self.amax = torch.zeros(1, dtype=torch.int32, device=device)
-            self.scale_inv = torch.ones(1, dtype=torch.float32, device=device)
-
-    @property
-    def scale_ptr(self):
-        return self.scale_inv.data_ptr() if self.scaled else 0
-
-    def refresh(self, stream):
-        sig = tuple((p.data_ptr(), p._version) for p in self.deps)
-        if sig == self.sig:
-            return
-        src = self.src_fn().detach().contiguous().float()
-        cin_p, cout_p = C.c_int32(0), C.c_int32(0)
-        lib = L.load()
-        if self.scaled:
-            amax = None
-            if len(self.deps) == 1 and src.data_ptr() == self.deps[0].data_ptr():
-                # the whole parameter, already reduced by the forward pack at this version (same stream, earlier)
-                from .unet import AMAX_OF
-                hit = AMAX_OF.get(self.deps[0].data_ptr())
-                if hit is not None and hit[0] == self.deps[0]._version and hit[2]() is self.deps[0]:
-                    amax = hit[1]
-            if amax is None:
-                amax = self.amax
-                amax.zero_()
-                L.check(lib.sgd_weight_amax(_ptr(src), src.numel(), _ptr(amax), stream), "sgd_weight_amax")
-            L.check(lib.sgd_pack_weight_scaled(_ptr(src), _ptr(self.buf), self.cout_fwd, self.cin_fwd, self.ksize, self.prec,
-                                               1, _ptr(amax), _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p),
-                                               stream), "sgd_pack_weight_scaled")
-        else:
-            L.check(lib.sgd_pack_weight_dgrad(_ptr(src), _ptr(self.buf), self.cout_fwd, self.cin_fwd, self.ksize,
-                                              self.prec, C.byref(cin_p), C.byref(cout_p), stream), "pack_dgrad")
-        self.cin_p, self.cout_p = cin_p.value, cout_p.value
-        self._keep = src
-        self.sig = sig
 
 
 def wgrad_ksplit(taps, cout, cin, rows):
@@ -254,8 +204,9 @@ class Backward:
             self.prog.add(f"bucket{bi}.allreduce", bucket_ready)
 
     def dgrad(self, tag, gy, cin_of_gy, y, cout_of_y, deps, src_fn, cout_fwd, cin_fwd, ksize, conv=None, m=0,
-              y_ld=None, zero_up=False, acc=False):
-        """y (+)= adjoint(W) applied to gy (gy has cout_fwd channels, y gets cin_fwd channels).
+              y_ld=None, zero_up=False, acc=False, pad=None, donor=None):
+        """y (+)= adjoint(W) applied to gy (gy has cout_fwd channels, y gets cin_fwd channels).  W [cout_fwd, cin_fwd(, k, k)]:
+        the parameters `deps` (zero-padded: pad), or what src_fn returns of them; donor: packs.Packed.
         zero_up: adjoint of a stride-2 conv (gy is zero-upsampled x2 inside the loader); acc: add into y."""
         # the head (a conv with 3 / 4 OUTPUT channels): its input gradient is the stem's kernel on the flipped, transposed
         # parameter (csrc/narrow.hip, adjoint mode) -- fp32 FMA straight from the weight, no adjoint pack
@@ -270,7 +221,7 @@ class Backward:
                           ld, 1, stream)
             self.prog.add(tag, sgd_conv3_narrow_in, flops=2.0 * nimg * hh * ww * cout_of_y * 9 * cin_of_gy)
             return
-        pk = _PackedAdj(deps, src_fn, cout_fwd, cin_fwd, ksize, self.prec, self.dev)
+        pk = Packed(deps, ksize, self.prec, L.PACK_DGRAD, pad, src_fn, (cout_fwd, cin_fwd), donor, self.dev)
         self.packs.append(pk)
         a = L.IgemmArgs()
         a.x0, a.c0 = gy.data_ptr(), cin_of_gy
@@ -283,7 +234,7 @@ class Backward:
                 a.mode, a.n, a.hi, a.wi, a.ho, a.wo, a.stride = L.MODE_CONV3, nimg, hh, ww, hh, ww, 1
         else:
             a.mode, a.m, a.stride = L.MODE_FLAT, m, 1
-        a.w = pk.buf.data_ptr()
+        a.w, a.cin_p, a.cout_p = pk.buf.data_ptr(), pk.cin_p, pk.cout_p
         a.w_scale_inv = pk.scale_ptr
         a.y, a.cout, a.y_ld, a.prec = y.data_ptr(), cout_of_y, (y_ld or cout_of_y), self.prec
         if acc:
@@ -344,13 +295,12 @@ class Backward:
     def dx(self, layer, gy, dst, acc=False, tag=None):
         """dst (+)= the gradient of the layer's input, from the gradient gy of its output"""
         g, pk = gemm_geometry(layer.a), layer.pk
-        w, = pk.srcs
-        src_fn = (lambda: w) if pk.pad is None else (lambda: pk.pad.apply(w.detach().float()))
-        self.dgrad(tag or _tag(layer) + ".dgrad", gy, g.cout, dst, g.cin, pk.srcs, src_fn, g.cout, g.cin,
-                   pk.ksize, conv=g.conv, m=0 if g.conv else g.rows, zero_up=g.zero_up, acc=acc)
+        assert len(pk.srcs) == 1
+        self.dgrad(tag or _tag(layer) + ".dgrad", gy, g.cout, dst, g.cin, pk.srcs, None, g.cout, g.cin,
+                   pk.ksize, conv=g.conv, m=0 if g.conv else g.rows, zero_up=g.zero_up, acc=acc, pad=pk.pad, donor=pk)
 
     def dw(self, layer, gy):
-        """the layer's weight (and bias) gradient.  A zero-padded operator (unet._Pad; the descriptor's widths are the PADDED
+        """the layer's weight (and bias) gradient.  A zero-padded operator (packs._Pad; the descriptor's widths are the PADDED
         ones): the padded gradient is gathered back into the parameter's own shape -- the padding rows / columns receive
         gradients that belong to no parameter -- and the bias gradient is the column sums of gy, gathered like the weight's
         rows where the bias is padded too."""
@@ -385,7 +335,7 @@ class Backward:
             self.colsum(tag + ".dbeta", _ptr(g), rows, c, c, beta_name)
 
     def gather_op(self, tag, pname, padded, pad):
-        """parameter gradient <- the entries of a zero-padded gradient that belong to the parameter (unet._Pad.gather)"""
+        """parameter gradient <- the entries of a zero-padded gradient that belong to the parameter (packs._Pad.gather)"""
         dst = self.pg(pname)
 
         def op(stream):
@@ -659,15 +609,10 @@ class Backward:
         skinny = n <= 256 and fw >= 2048 and os.environ.get("SGDM_SKINNY_DGRAD", "1") != "0"
         if skinny:
             wcat = self.buf(fw, ech)
-            box = dict(sig=None)
 
-            def refresh_wcat(stream, wcat=wcat, box=box):
-                sig = tuple((w.data_ptr(), w._version) for w in wparams)
-                if sig != box["sig"]:
-                    torch.cat([w.detach().float() for w in wparams], 0, out=wcat)
-                    box["sig"] = sig
-                return 0
-            self.prog.add("emb_layers.wcat", refresh_wcat)
+            def refresh_wcat(stream, wcat=wcat):
+                torch.cat([w.detach().float() for w in wparams], 0, out=wcat)
+            self.prog.add("emb_layers.wcat", Derived(wparams, refresh_wcat))
             # y[n, ech] = sum_k gfilm[n, k] wcat[k, ech] IS a weight gradient seen from the other side: "rows" = the fw FiLM
             # outputs, "gy" = gfilm transposed (fw x n), "a" = wcat.  The split 1x1 weight-gradient kernel (MFMA, split K over
             # the rows) replaces the fp32-FMA sgd_linear_splitk_t (LDS-bound: 0.25 ms per step at C2 for 1.7 GFLOP)
@@ -802,10 +747,8 @@ class Backward:
         lib = self.lib
         stream = torch.cuda.current_stream().cuda_stream
         if self._pack_batch is None or len(self._pack_batch.packs) != len(self.packs):
-            self._pack_batch = _PackBatch(self.packs, self.prec, self.dev)
+            self._pack_batch = PackBatch(self.packs, self.prec, self.dev)
         self._pack_batch.refresh(stream)
-        for a, pk in self.late:
-            a.cin_p, a.cout_p = pk.cin_p, pk.cout_p
         n, c = self.n, self.m.out_channels
         h, w = self.e.h, self.e.w
         g = (geps_nchw.float() * self.gscale).contiguous()
@@ -819,7 +762,6 @@ class Backward:
         # poisoned step is never applied -- and copied to pinned host memory for the next step's poll_health() to raise on.
         word, flag = self.e.health_word(), None
         if word is not None:
-            from .unet import grad_health
             flag = self.arena.health if self.arena is not None else self._own_flag()
             flag.copy_(word.ne(0))
         if self.reducer is not None:
@@ -959,17 +901,6 @@ def make_backward(eng):
     # RCCL: a communicator of the exchange's own, capped at the CU reserve (collective over all ranks: every rank builds
     # its backward program at its first training step)
     return Backward(eng, arena, BucketReducer(arena, group=exchange_group(), average=False, force=exchange_forced(eng.m)))
-
-
-def refuse_inference_only(model):
-    """the single-product modes (hip_precision 'f16' / 'bf16') have no backward: half-precision training needs loss-scale and
-    master-weight decisions this library has not made.  Raises before anything is launched."""
-    mods = model.modules() if isinstance(model, torch.nn.Module) else ()
-    for mod in mods:
-        name = getattr(mod, "hip_precision", None)
-        if name in L.INFERENCE_ONLY:
-            raise ValueError(f"hip_precision='{name}' is inference only (operands rounded once to 16 bits, no backward): "
-                             f"train with 'f32', 'f16x3' or 'bf16x3', or run this model under torch.no_grad() / eval()")
 
 
 def forward_train(model, x, t, cond, layout, mask, n):

@@ -14,7 +14,6 @@ HIP library or a GPU the forward raises.
 """
 import collections
 import ctypes as C
-import weakref
 import math
 import os
 
@@ -22,13 +21,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .packs import Derived, FusedPacked, PackBatch, Packed, Stale, _Pad, _ptr  # noqa: F401  (_Pad, _ptr: taken from here too)
 
 GN_GROUPS, GN_EPS, LN_EPS = 32, 1e-5, 1e-5
 NUM_TIME_TOKENS = NUM_COND_TOKENS = 8
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def timestep_freqs(dim, max_period=10000):
@@ -110,13 +106,6 @@ class _Spec:
         self.items.append((p + ".bias", (c,), "param", _zeros))
 
 
-# ------------------------------------------------------------------------------------------------
-# packed weights
-# ------------------------------------------------------------------------------------------------
-AMAX_OF = {}       # parameter data_ptr -> (version, device int32 holding the bits of max |w|, weakref to the parameter:
-                   # an address can be recycled by another tensor), written by _Packed.refresh
-
-
 HEAD_DIMS = (16, 32, 64, 128)          # head widths the MFMA attention cores are instantiated for
 
 
@@ -128,248 +117,6 @@ def padded_head_dim(d):
         if dp >= d:
             return dp
     raise ValueError(f"attention head width {d} > {HEAD_DIMS[-1]} is not supported")
-
-
-class _Pad:
-    """zero-padded re-layout of a 2-D weight (or a vector / [2, d] table along its last dim): source row r lands at row
-    rows[r], source column c at column cols[c] of an [n_rows, n_cols] zero matrix.  ``gather`` is the adjoint (the
-    gradient of the padded tensor read back at the positions of the real entries)."""
-
-    def __init__(self, rows=None, n_rows=None, cols=None, n_cols=None):
-        self.rows = None if rows is None else torch.as_tensor(rows, dtype=torch.int64)
-        self.cols = None if cols is None else torch.as_tensor(cols, dtype=torch.int64)
-        self.n_rows, self.n_cols = n_rows, n_cols
-
-    def _idx(self, dev):
-        if self.rows is not None and self.rows.device != dev:
-            self.rows = self.rows.to(dev)
-        if self.cols is not None and self.cols.device != dev:
-            self.cols = self.cols.to(dev)
-
-    def apply(self, w):
-        self._idx(w.device)
-        w2 = w.reshape(w.shape[0], -1)
-        out = w2.new_zeros(self.n_rows if self.rows is not None else w2.shape[0],
-                           self.n_cols if self.cols is not None else w2.shape[1])
-        if self.rows is not None and self.cols is not None:
-            out[self.rows[:, None], self.cols[None, :]] = w2
-        elif self.rows is not None:
-            out[self.rows] = w2
-        else:
-            out[:, self.cols] = w2
-        return out
-
-    def gather(self, wp):
-        self._idx(wp.device)
-        if self.rows is not None:
-            wp = wp[self.rows]
-        if self.cols is not None:
-            wp = wp[:, self.cols]
-        return wp
-
-
-class _Packed:
-    """device buffer holding one conv/linear weight in the igemm layout, refreshed when the source
-    parameter(s) change (optimizer step / load_state_dict bump ``_version``)."""
-
-    def __init__(self, srcs, ksize, prec, pad=None, subpixel=False):
-        self.srcs = srcs                     # list of parameters concatenated along dim 0
-        self.names = ()                      # their names (_Engine.pack)
-        self.ksize = ksize
-        self.prec = prec
-        self.pad = pad                       # _Pad: the packed operator is the zero-padded re-layout of the parameter
-        # subpixel: the 16 summed 2x2 kernels of a nearest-x2-upsample 3x3 conv (include/sgdm_hip.h: SGD_RS_UP2_SUBPIXEL),
-        # split modes only; its scale is that of max |V|, so it never lends its amax to the adjoint pack (AMAX_OF)
-        self.subpixel = subpixel
-        assert not subpixel or (ksize == 3 and pad is None and prec != L.PREC_F32)
-        self.cout = sum(s.shape[0] for s in srcs)
-        self.cin = srcs[0].shape[1]
-        if pad is not None:
-            assert ksize == 1
-            self.cout = pad.n_rows if pad.rows is not None else self.cout
-            self.cin = pad.n_cols if pad.cols is not None else self.cin
-        lib = L.load()
-        nbytes = (lib.sgd_packed_weight_subpixel_bytes(self.cout, self.cin, prec) if subpixel
-                  else lib.sgd_packed_weight_bytes(self.cout, self.cin, ksize, prec))
-        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=srcs[0].device)
-        self.cin_p = self.cout_p = 0
-        self.sig = None
-        # idle: a pack only the TRAINING forward launches (the pair of a fused ResBlock) while the engine prepares an inference
-        # evaluation -- refresh() leaves it stale until the next training forward (_Engine.refresh)
-        self.idle = False
-        # split precisions: per-tensor power-of-two scale so hi AND lo halves stay in fp16's normal range whatever the
-        # tensor's magnitude (include/sgdm_hip.h: sgd_igemm_args.w_scale_inv); formed on the device, no host round trip
-        self.scaled = prec != L.PREC_F32
-        if self.scaled:
-            self.amax = torch.zeros(1, dtype=torch.int32, device=srcs[0].device)
-            self.scale_inv = torch.ones(1, dtype=torch.float32, device=srcs[0].device)
-
-    @property
-    def scale_ptr(self):
-        return self.scale_inv.data_ptr() if self.scaled else 0
-
-    def refresh(self, stream):
-        sig = tuple((s.data_ptr(), s._version) for s in self.srcs)
-        if sig == self.sig or self.idle:
-            return
-        lib = L.load()
-        src = self.srcs[0].detach() if len(self.srcs) == 1 else torch.cat([s.detach() for s in self.srcs], 0)
-        src = src.contiguous().float()
-        if self.pad is not None:
-            src = self.pad.apply(src).contiguous()
-        cin_p, cout_p = C.c_int32(0), C.c_int32(0)
-        if self.subpixel:
-            self.amax.zero_()
-            L.check(lib.sgd_weight_amax_subpixel(_ptr(src), self.cout, self.cin, _ptr(self.amax), stream), "sgd_weight_amax_subpixel")
-            L.check(lib.sgd_pack_weight_subpixel_scaled(_ptr(src), _ptr(self.buf), self.cout, self.cin, self.prec, _ptr(self.amax),
-                                                        _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p), stream),
-                    "sgd_pack_weight_subpixel_scaled")
-        elif self.scaled:
-            self.amax.zero_()
-            L.check(lib.sgd_weight_amax(_ptr(src), src.numel(), _ptr(self.amax), stream), "sgd_weight_amax")
-            if len(self.srcs) == 1 and self.pad is None:
-                # max |w| of this parameter at this version: the adjoint pack of the same tensor (train._PackedAdj) reuses it
-                AMAX_OF[self.srcs[0].data_ptr()] = (self.srcs[0]._version, self.amax, weakref.ref(self.srcs[0]))
-            L.check(lib.sgd_pack_weight_scaled(_ptr(src), _ptr(self.buf), self.cout, self.cin, self.ksize, self.prec, 0,
-                                               _ptr(self.amax), _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p),
-                                               stream), "sgd_pack_weight_scaled")
-        else:
-            L.check(lib.sgd_pack_weight(_ptr(src), _ptr(self.buf), self.cout, self.cin, self.ksize, self.prec,
-                                        C.byref(cin_p), C.byref(cout_p), stream), "sgd_pack_weight")
-        self.cin_p, self.cout_p = cin_p.value, cout_p.value
-        self._keep = src
-        self.sig = sig
-
-
-class _FusedPacked:
-    """A channel-changing ResBlock's out_layers.3 (3x3) and skip_connection (1x1) weights packed back to back for
-    sgd_igemm_fused_aux: the two products share their accumulators, so both tensors carry the scale of ONE amax folded over
-    both; the launch's bias is the sum of the two biases.  Follows all four parameters' versions; refreshed only in front of an
-    inference evaluation (the training forward launches the pair from their own packs)."""
-
-    def __init__(self, w3, w1, b3, b1, prec):
-        self.srcs, self.names, self.prec = [w3, w1, b3, b1], (), prec
-        self.cout, self.cin, self.caux = w3.shape[0], w3.shape[1], w1.shape[1]
-        assert w1.shape[0] == self.cout and prec != L.PREC_F32
-        lib = L.load()
-        self.off1 = int(lib.sgd_packed_weight_bytes(self.cout, self.cin, 3, prec))      # the 1x1 units follow the 3x3 ones
-        nbytes = self.off1 + int(lib.sgd_packed_weight_bytes(self.cout, self.caux, 1, prec))
-        dev = w3.device
-        self.buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        self.bias = torch.empty(self.cout, dtype=torch.float32, device=dev)
-        self.amax = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.scale_inv = torch.ones(1, dtype=torch.float32, device=dev)
-        self.cin_p = self.cout_p = 0
-        self.sig = None
-
-    @property
-    def scale_ptr(self):
-        return self.scale_inv.data_ptr()
-
-    def refresh(self, stream):
-        sig = tuple((s.data_ptr(), s._version) for s in self.srcs)
-        if sig == self.sig:
-            return
-        lib = L.load()
-        w3, w1 = (s.detach().contiguous().float() for s in self.srcs[:2])
-        self.amax.zero_()
-        for w in (w3, w1):
-            L.check(lib.sgd_weight_amax(_ptr(w), w.numel(), _ptr(self.amax), stream), "sgd_weight_amax")
-        cin_p, cout_p, cx_p = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        L.check(lib.sgd_pack_weight_scaled(_ptr(w3), _ptr(self.buf), self.cout, self.cin, 3, self.prec, 0, _ptr(self.amax),
-                                           _ptr(self.scale_inv), C.byref(cin_p), C.byref(cout_p), stream), "sgd_pack_weight_scaled")
-        L.check(lib.sgd_pack_weight_scaled(_ptr(w1), C.c_void_p(self.buf.data_ptr() + self.off1), self.cout, self.caux, 1,
-                                           self.prec, 0, _ptr(self.amax), _ptr(self.scale_inv), C.byref(cx_p), C.byref(cout_p),
-                                           stream), "sgd_pack_weight_scaled")
-        torch.add(self.srcs[2].detach().float(), self.srcs[3].detach().float(), out=self.bias)
-        self.cin_p, self.cout_p = cin_p.value, cout_p.value
-        self._keep = (w3, w1)
-        self.sig = sig
-
-
-class _PackBatch:
-    """the weight packs of one launch program refreshed together: when (almost) all of them are stale -- every step of a
-    training loop -- ONE sgd_pack_weights_batched call (zero + amax + pack kernels over a device-side job table) replaces
-    two launches per tensor (142 pack + 74 amax launches of ~6 us per step at C2).  Members are `_Packed` /
-    `train._PackedAdj` objects whose source is one whole contiguous fp32 parameter; the others (concatenated FiLM
-    projections, zero-padded head re-layouts, sliced sources) keep their own refresh."""
-
-    MIN_STALE = 8           # fewer stale packs than this: refresh them one by one
-
-    def __init__(self, packs, prec, dev):
-        self.packs, self.prec, self.dev = list(packs), prec, dev
-        self.lib = L.load()
-        self.members, self.table_sig = None, None
-
-    @staticmethod
-    def _source(pk):
-        """(parameter, forward cout, forward cin, transpose) of a batchable pack, else None"""
-        if hasattr(pk, "srcs"):                                   # unet._Packed
-            if len(pk.srcs) != 1 or pk.pad is not None:
-                return None
-            p, t = pk.srcs[0], (L.PACK_SUBPIXEL if pk.subpixel else L.PACK_FORWARD)
-            cout, cin = pk.cout, pk.cin
-        else:                                                     # train._PackedAdj
-            if len(pk.deps) != 1:
-                return None
-            p, t = pk.deps[0], 1
-            src = pk.src_fn()
-            if src.data_ptr() != p.data_ptr() or src.numel() != p.numel():
-                return None
-            cout, cin = pk.cout_fwd, pk.cin_fwd
-        if p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != cout * cin * pk.ksize * pk.ksize:
-            return None
-        return p, cout, cin, t
-
-    def _build(self):
-        members, jobs = [], []
-        ab, pb = C.c_int32(), C.c_int32()
-        cp, op = C.c_int32(), C.c_int32()
-        a_job, a_first, p_job, p_first = [], [0], [], [0]
-        scaled = self.prec != L.PREC_F32
-        for pk in self.packs:
-            srcd = self._source(pk)
-            if srcd is None:
-                continue
-            p, cout, cin, t = srcd
-            L.check(self.lib.sgd_pack_job_blocks(cout, cin, pk.ksize, self.prec, t, C.byref(ab), C.byref(pb), C.byref(cp),
-                                                 C.byref(op)), "sgd_pack_job_blocks")
-            j = len(members)
-            jobs.append(L.PackJob(src=p.data_ptr(), dst=pk.buf.data_ptr(), amax_bits=pk.amax.data_ptr() if scaled else 0,
-                                  scale_inv=pk.scale_inv.data_ptr() if scaled else 0, cout=cout, cin=cin, ksize=pk.ksize,
-                                  transpose=t, own_amax=1 if scaled else 0))
-            members.append((pk, p, cp.value, op.value))
-            a_job += [j] * (ab.value if scaled else 0)
-            a_first.append(len(a_job))
-            p_job += [j] * pb.value
-            p_first.append(len(p_job))
-        self.members = members
-        self.table_sig = tuple(p.data_ptr() for _, p, _, _ in members)
-        if not members:
-            return
-        arr = (L.PackJob * len(jobs))(*jobs)
-        self.jobs = torch.frombuffer(bytearray(C.string_at(C.addressof(arr), C.sizeof(arr))), dtype=torch.uint8).to(self.dev)
-        i32t = lambda v: torch.tensor(v if v else [0], dtype=torch.int32, device=self.dev)
-        self.a_job, self.a_first, self.p_job, self.p_first = i32t(a_job), i32t(a_first), i32t(p_job), i32t(p_first)
-        self.n_a, self.n_p = len(a_job), len(p_job)
-        self.batched = {id(pk) for pk, _, _, _ in members}
-
-    def refresh(self, stream):
-        if self.members is None or self.table_sig != tuple(p.data_ptr() for _, p, _, _ in self.members):
-            self._build()                                          # first use, or a parameter moved (.to(), re-materialised)
-        stale = [(pk, p, cp, op) for pk, p, cp, op in self.members
-                 if pk.sig != ((p.data_ptr(), p._version),) and not getattr(pk, "idle", False)]
-        if len(stale) >= self.MIN_STALE and os.environ.get("SGDM_BATCHED_PACK", "1") != "0":
-            L.check(self.lib.sgd_pack_weights_batched(_ptr(self.jobs), len(self.members), _ptr(self.a_job), _ptr(self.a_first),
-                                                      self.n_a, _ptr(self.p_job), _ptr(self.p_first), self.n_p, self.prec,
-                                                      stream), "sgd_pack_weights_batched")
-            for pk, p, cp, op in self.members:                     # (fresh and idle members were re-packed too: same bytes)
-                pk.cin_p, pk.cout_p = cp, op
-                pk.sig = ((p.data_ptr(), p._version),)
-                if hasattr(pk, "srcs") and pk.scaled and not pk.subpixel:
-                    AMAX_OF[p.data_ptr()] = (p._version, pk.amax, weakref.ref(p))
-        for pk in self.packs:                                      # the rest, and small stale sets, one by one
-            pk.refresh(stream)
 
 
 # One forward GEMM as the backward program needs it (train.Backward.dx / dw): the descriptor `a` (its geometry:
@@ -583,14 +330,14 @@ class UNetModelBase(nn.Module):
         run the head conv over weight rows [0, head) only -- ``eps_nhwc`` is then [n, H, W, head].  An engine of its own:
         the choice is part of the key (None, the default and the only training engine: every row)"""
         dev = self._device()
-        sig = tuple(p.data_ptr() for p in self._all_tensors())
         if head is not None and not 0 < head < self.out_channels:
             raise ValueError(f"head={head!r}: a proper prefix of the {self.out_channels} output channels")
         key = (n, h, w, prec) if head is None else (n, h, w, prec, head)
         eng = self._engines.get(key)
-        if eng is None or eng.sig != sig:
+        if eng is None or eng.built_on.changed():                  # a tensor moved: every pointer of the program is stale
             eng = _Engine(self, n, h, w, prec, dev, head)
-            eng.sig = sig
+            eng.built_on = Stale(self._all_tensors, versions=False)
+            eng.built_on.mark()
             self._engines[key] = eng
         return eng
 
@@ -687,7 +434,7 @@ class _Engine:
         # zeroed once, shared by every launch of this engine's programs -- they are ordered on one stream
         self.work_bytes = int(self.lib.sgd_igemm_work_bytes()) if os.environ.get("SGDM_BALANCE", "1") != "0" else 0
         self.work = torch.zeros(max(1, self.work_bytes // 4), dtype=torch.float32, device=dev)
-        self.fused_packs = []     # _FusedPacked of the ResBlocks whose inference forward runs sgd_igemm_fused_aux
+        self.fused_packs = []     # FusedPacked of the ResBlocks whose inference forward runs sgd_igemm_fused_aux
         self.train_packs = []     # the 3x3 / 1x1 packs of those blocks' pair: left stale while the engine serves inference
         self.train_bufs = []      # (shape, [(igemm args, field)]) of buffers only the training forward writes: allocated by its first use
         self._build()
@@ -720,7 +467,7 @@ class _Engine:
         return self._progs[bool(train)]
 
     def pack(self, names, ksize, pad=None, subpixel=False):
-        pk = _Packed([self.m.P(nm) for nm in names], ksize, self.prec, pad, subpixel)
+        pk = Packed([self.m.P(nm) for nm in names], ksize, self.prec, L.PACK_SUBPIXEL if subpixel else L.PACK_FORWARD, pad)
         pk.names = tuple(names)
         self.packed.append(pk)
         return pk
@@ -749,15 +496,11 @@ class _Engine:
         step with the parameter by refresh() like the packed weights"""
         src = self.m.P(name)
         buf = self.buf(*pad.apply(src.detach().reshape(-1, src.shape[-1]) if src.dim() > 1 else src.detach().reshape(1, -1)).shape)
-        box = dict(sig=None)
 
         def hook(stream):
-            sig = (src.data_ptr(), src._version)
-            if sig != box["sig"]:
-                v = src.detach().float()
-                buf.copy_(pad.apply(v.reshape(-1, v.shape[-1]) if v.dim() > 1 else v.reshape(1, -1)))
-                box["sig"] = sig
-        self.refresh_hooks.append(hook)
+            v = src.detach().float()
+            buf.copy_(pad.apply(v.reshape(-1, v.shape[-1]) if v.dim() > 1 else v.reshape(1, -1)))
+        self.refresh_hooks.append(Derived([src], hook))
         return buf
 
     def igemm(self, tag, x0, c0, y, cout, pk, *, x1=None, c1=0, conv=None, m=0, rows_per_n=0,
@@ -766,7 +509,7 @@ class _Engine:
         """stats=True: the epilogue also writes the GroupNorm statistics of y (consumed by gn() through
         sgd_stats_reduce instead of a sgd_chan_stats pass over the tensor).  y=None: the output pointer is set later
         (train_bufs; res_later: so is the residual's).  when: the program variant this launch belongs to (_Program.add).
-        aux=(x0, c0, x1, c1): the launch is sgd_igemm_fused_aux with this second input (pk: a _FusedPacked).
+        aux=(x0, c0, x1, c1): the launch is sgd_igemm_fused_aux with this second input (pk: a FusedPacked).
         bias: a parameter's name, (name, _Pad or None) for a parameter the launch reads as a zero-padded copy, or a tensor that
         is no parameter.  Returns the layer's record (_Layer)."""
         bias_name = bias_pad = None
@@ -788,7 +531,7 @@ class _Engine:
         a.pa = pa.data_ptr() if pa is not None else 0
         a.pb = pb.data_ptr() if pb is not None else 0
         a.pc = pc.data_ptr() if pc is not None else 0
-        a.w = pk.buf.data_ptr()
+        a.w, a.cin_p, a.cout_p = pk.buf.data_ptr(), pk.cin_p, pk.cout_p
         a.w_scale_inv = pk.scale_ptr
         a.bias = bias.data_ptr() if bias is not None else 0
         a.res = res.data_ptr() if res is not None else 0
@@ -823,7 +566,7 @@ class _Engine:
                 a.stats = sbuf.data_ptr()
                 self.stats_of[y.data_ptr()] = (sbuf, parts, cout)
         self.prog.keep.append((a, pk))
-        self._late.append((a, pk))                # cin_p / cout_p are known after the first pack
+        self._late.append((a, pk))                # every igemm descriptor of the forward with its pack
         # algorithmic work of this launch: 2*M*N*K flops; every input/output element moved once + weights
         rows = conv[0] * conv[3] * conv[4] if conv is not None else m
         rows_in = conv[0] * conv[1] * conv[2] if conv is not None else m
@@ -850,14 +593,10 @@ class _Engine:
         elif narrow_out:
             wsrc, fn = pk.srcs[0], self.lib.sgd_conv3_narrow_out
             w9 = self.buf(9, cout, c0)
-            box = dict(sig=None)
 
-            def refresh_w9(stream, w9=w9, wsrc=wsrc, box=box):
-                sig = (wsrc.data_ptr(), wsrc._version)
-                if sig != box["sig"]:
-                    w9.copy_(wsrc.detach().float().permute(2, 3, 0, 1).reshape(9, cout, c0))
-                    box["sig"] = sig
-            self.refresh_hooks.append(refresh_w9)
+            def refresh_w9(stream, w9=w9, wsrc=wsrc):
+                w9.copy_(wsrc.detach().float().permute(2, 3, 0, 1).reshape(9, cout, c0))
+            self.refresh_hooks.append(Derived([wsrc], refresh_w9))
             x_p, y_p, b_p, w_p = _ptr(x0), C.c_void_p(a.y), C.c_void_p(a.bias or 0), _ptr(w9)
             pa_p, pb_p = C.c_void_p(a.pa or 0), C.c_void_p(a.pb or 0)
             nimg, ho, wo, y_ld = conv[0], conv[3], conv[4], a.y_ld
@@ -930,8 +669,10 @@ class _Engine:
         film_w = sum(fm * co for _, co in res_names)
         film = self.buf(n, film_w)
         fbias = self.buf(film_w)
-        self._film_bias_src = [P(p + ".emb_layers.1.bias") for p, _ in res_names]
-        self._film_bias = fbias
+        fbias_src = [P(p + ".emb_layers.1.bias") for p, _ in res_names]
+
+        def refresh_film_bias(stream):
+            fbias.copy_(torch.cat([b.detach().reshape(-1) for b in fbias_src]))
         ec = self.emb_c
         af = self.igemm("emb_layers", emb, ted, film, film_w,
                         self.pack([p + ".emb_layers.1.weight" for p, _ in res_names], 1), m=n, silu=1, bias=fbias,
@@ -962,13 +703,14 @@ class _Engine:
             # rows [0, head) of the head conv: contiguous views of the two parameters (same storage and version counter, so
             # the pack follows the parameter like any other)
             oc, hbias = self.head, P("out.2.bias").detach()[:self.head]
-            hpk = _Packed([P("out.2.weight").detach()[:oc]], 3, self.prec, None, False)
+            hpk = Packed([P("out.2.weight").detach()[:oc]], 3, self.prec)
             self.packed.append(hpk)
         self.eps_nhwc = self.buf(n, hh, ww, oc)
         ah = self.igemm("out.2", t, c, self.eps_nhwc, oc, hpk,
                         conv=(n, hh, ww, hh, ww, 1, L.RS_NONE), pro=L.PRO_AFFINE_NC, silu=1, pa=a, pb=b,
                         bias=hbias)
         self.tape.append(dict(kind="head", x=t, a=a, b=b, sums=self._last_sums, conv=ah))
+        self.refresh_hooks.append(Derived(fbias_src, refresh_film_bias))
 
     def _block(self, prefix, blk, srcs):
         """srcs: list of (tensor, C, H, W) (two entries = virtual concat [h, skip])"""
@@ -1056,8 +798,8 @@ class _Engine:
             # y = conv3x3(act(h1)) + conv1x1(x) + b3 + bs as ONE GEMM over K = 9 cout + cin (sgd_igemm_fused_aux): no skip tensor
             # written and read back, eleven launches fewer per evaluation of the flagship model
             self.train_bufs.append(((n, hh, ww, cout), [(ask.a, "y"), (ac2.a, "res")]))
-            fpk = _FusedPacked(P(p + ".out_layers.3.weight"), P(p + ".skip_connection.weight"), P(p + ".out_layers.3.bias"),
-                               P(p + ".skip_connection.bias"), self.prec)
+            fpk = FusedPacked(P(p + ".out_layers.3.weight"), P(p + ".skip_connection.weight"), P(p + ".out_layers.3.bias"),
+                              P(p + ".skip_connection.bias"), self.prec)
             self.fused_packs.append(fpk)
             self.train_packs += [pks, pk2]
             self.igemm(p + ".out_layers.3", h1, cout, y, cout, fpk, bias=fpk.bias, when="infer", aux=(t0, c0, t1, c1), **kw2)
@@ -1090,19 +832,13 @@ class _Engine:
         for pk in self.train_packs:                # inference: neither the pair's packs nor (training) the fused ones are repacked
             pk.idle = not train
         if getattr(self, "_pack_batch", None) is None or len(self._pack_batch.packs) != len(self.packed):
-            self._pack_batch = _PackBatch(self.packed, self.prec, self.dev)
+            self._pack_batch = PackBatch(self.packed, self.prec, self.dev)
         self._pack_batch.refresh(stream)
         if not train:
             for pk in self.fused_packs:
                 pk.refresh(stream)
-        for a, pk in self._late:
-            a.cin_p, a.cout_p = pk.cin_p, pk.cout_p
         for hook in self.refresh_hooks:
             hook(stream)
-        sig = tuple((b.data_ptr(), b._version) for b in self._film_bias_src)
-        if sig != getattr(self, "_film_sig", None):
-            self._film_bias.copy_(torch.cat([b.detach().reshape(-1) for b in self._film_bias_src]))
-            self._film_sig = sig
 
     # ---- balanced-tail health word (include/sgdm_hip.h: sgd_igemm_work_status_offset).  A finisher whose producers did not
     # arrive within its bounded poll poisons its tile with NaN and raises the word; from then on every split tile on this
@@ -1426,7 +1162,6 @@ class UNetModel(UNetModelBase):
             nwork = eng.buf(ksplit, 1, nout)
             eng.gather_cond = True
             eng.sparse_cond = 8 * K <= 64 * 1024 - 2048 and os.environ.get("SGDM_SPARSE_COND", "1") != "0"
-            box = dict(sig=None)
 
             def mlp_cond0(stream):
                 """dense skinny GEMM for one-hot / float cond rows; for class / cluster IDS the same result as a column
@@ -1448,13 +1183,9 @@ class UNetModel(UNetModelBase):
                 changes.  It runs from Engine.refresh -- OUTSIDE the launch program -- so a hipGraph-captured step, which
                 holds only the gather, reads the current projection after an optimizer step / EMA swap / load_state_dict
                 (begin() of a captured trajectory calls refresh)."""
-                srcs = (wt, bs, self.null_cond_emb)
-                sig = tuple((s_.data_ptr(), s_._version) for s_ in srcs)
-                if sig != box["sig"]:
-                    L.check(lib.sgd_linear_splitk(_ptr(self.null_cond_emb), K, _ptr(wt), _ptr(bs), 1, nout, K, _ptr(nwork),
-                                                  ksplit, _ptr(nullproj), nout, stream), "sgd_linear_splitk(null)")
-                    box["sig"] = sig
-            eng.refresh_hooks.append(refresh_nullproj)
+                L.check(lib.sgd_linear_splitk(_ptr(self.null_cond_emb), K, _ptr(wt), _ptr(bs), 1, nout, K, _ptr(nwork),
+                                              ksplit, _ptr(nullproj), nout, stream), "sgd_linear_splitk(null)")
+            eng.refresh_hooks.append(Derived(lambda: (wt, bs, self.null_cond_emb), refresh_nullproj))
             eng.prog.add("mlp_cond.0", mlp_cond0, flops=2.0 * n * K * nout, nbytes=4.0 * (n * K + K * nout + n * nout))
             eng.prog.keep.append((wt, bs))
         a2 = eng.igemm("mlp_cond.2", c1, ted // 2, eng.emb_c, ted // 2, eng.pack(["mlp_cond.2.weight"], 1), m=eng.n,
