@@ -322,6 +322,16 @@ int sgd_attention_split(const float* q, int32_t q_ld, int32_t q_hs,
                         const float* k, const float* v, int32_t kv_ld, int32_t kv_hs,
                         int32_t batch, int32_t heads, int32_t tq, int32_t tk, int32_t d, float scale,
                         float* out, int32_t out_ld, float* lse, void* stream);
+/* The attention core with the attention map replaced by the IDENTITY (perturbed-attention guidance, Ahn et al. 2024: the
+ * perturbed half of a self-attention layer): out[b, i, h*d + j] = v[b, i*kv_ld + h*kv_hs + j], what sgd_attention would write
+ * if every softmax row were the unit vector on the query's own key (tq == tk == t).  No QK^T, no softmax, no PV: a strided
+ * gather, HBM-bound and exact in every arithmetic mode.  The addressing contract of the cores above: d in {16, 32, 64, 128},
+ * 16-byte accesses, v and out 16-byte aligned, kv_ld, kv_hs and out_ld multiples of 4 floats, out_ld >= heads*d -- anything
+ * else is SGD_ERR_ARG, nothing launched; row strides may exceed the minimum (padding columns are neither read nor written).
+ * Additive entry (ABI unchanged at 25). */
+int sgd_attention_identity(const float* v, int32_t kv_ld, int32_t kv_hs,
+                           int32_t batch, int32_t heads, int32_t t, int32_t d,
+                           float* out, int32_t out_ld, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Small glue kernels on the UNet boundary.

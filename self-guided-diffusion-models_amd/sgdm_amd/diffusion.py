@@ -38,6 +38,10 @@ Also without a counterpart, progressive distillation (Salimans & Ho 2022, Algori
 five scalars per grid point with which the target is linear in z_t and the teacher's two outputs) makes ``losses.p_losses_hip``
 train ONE DDIM step of the student against TWO of the frozen teacher (include/sgdm_hip.h: sgd_pd_half_step, sgd_pd_loss_fwd /
 sgd_pd_loss_bwd), ``train.progressive_next_stage`` halves K, and ``p_sample_loop`` walks the student's K steps by default.
+Also without a counterpart, perturbed-attention guidance (Ahn et al. 2024): the sampling kwargs ``pag_scale`` = s, ``pag_layers`` and
+``pag_drop_cond`` (``pag_options``) make the second half of the doubled evaluation the same network with the self-attention map of
+the chosen layers replaced by the identity (unet.py: ``_engine(pag=...)``, include/sgdm_hip.h: sgd_attention_identity); the step
+kernels read the halves in their cfg form with w = s, in all five samplers; ``cond_scale`` is not read.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -353,6 +357,54 @@ def cfg_distilled_option(sk):
     return bool(on)
 
 
+def pag_scale_option(sk):
+    """the sampling kwarg ``pag_scale`` (perturbed-attention guidance, Ahn et al. 2024): a finite number >= 0; 0, the default,
+    is off.  ValueError for anything else (a bool included).  Pure host code."""
+    s = (sk or {}).get("pag_scale", 0)
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= s < float("inf"):
+        raise ValueError(f"pag_scale={s!r}: a finite number >= 0 (0: off)")               # (NaN fails the comparison)
+    return float(s)
+
+
+def pag_options(sk, fused=True, model=None):
+    """None (off), or ``(s, layers, drop_cond)`` of the sampling kwargs ``pag_scale`` / ``pag_layers`` / ``pag_drop_cond``:
+    perturbed-attention guidance, eps_c + s (eps_c - eps_p) with eps_p the SAME network whose self-attention map is the
+    identity in ``layers`` -- the cfg form of the step kernels with u := eps_p and w := s, whatever the model's scale_type;
+    ``cond_scale`` is not read.  ``layers``: a sorted tuple of attention-layer prefixes of ``model`` -- from 'mid' (default, the
+    middle block's attention), 'all', or a list of prefixes.  ``drop_cond`` (default False): the perturbed half also drops the
+    condition, drop probabilities (0, 1) as for CFG instead of (0, 0).  ValueError, before anything is loaded or launched, for
+    a value out of range, an unknown prefix or a selection of nothing, ``pag_layers`` / ``pag_drop_cond`` without
+    ``pag_scale > 0``, ``cfg_distilled`` (one evaluation per step: no second half), a step that is not the drop-in UNet's fused
+    one (``fused``: _StepRunner.fused_cfg() -- a generic denoise_sample_fn, p0, a tensor cond_scale) and a model whose
+    attention is not the self-attention block (unetca_fast, use_spatial_transformer).  Pure host code: no device, no library."""
+    sk = sk or {}
+    s = pag_scale_option(sk)
+    layers, drop = sk.get("pag_layers"), sk.get("pag_drop_cond")
+    if s == 0:
+        if layers is not None or drop is not None:
+            raise ValueError("pag_layers / pag_drop_cond without pag_scale > 0")
+        return None
+    if cfg_distilled_option(sk):
+        raise ValueError("pag_scale with cfg_distilled: a distilled student has one (conditional) evaluation per step, there "
+                         "is no perturbed half to guide with")
+    if not fused or model is None:
+        raise ValueError("pag_scale needs the fused step: the drop-in UNet's forward_with_cond_scale as denoise_sample_fn, no "
+                         "p0 and no tensor cond_scale")
+    if drop is not None and not isinstance(drop, (bool, np.bool_)):
+        raise ValueError(f"pag_drop_cond={drop!r} (True or False)")
+    known = model.attention_prefixes()
+    if layers is None or (isinstance(layers, str) and layers == "mid"):
+        want = [p for p in known if p.startswith("middle_block.")]
+    elif isinstance(layers, str) and layers == "all":
+        want = known
+    elif isinstance(layers, (list, tuple)) and all(isinstance(p, str) for p in layers):
+        want = list(layers)
+    else:
+        raise ValueError(f"pag_layers={layers!r}: 'mid', 'all' or a list of attention-layer prefixes ({known})")
+    # the engine's own check of its ``pag`` argument (2: any even UNet batch): the model kind, unknown prefixes, an empty set
+    return s, model._pag_set(tuple(sorted(set(want))), 2), bool(drop)
+
+
 V_FORM_SAMPLERS = ("native", "ddim", "dpmsolver")
 
 
@@ -488,14 +540,20 @@ class _StepRunner:
     outside the interval is ONE UNet evaluation at B, nothing dropped.  On the data form of 'v' (``form`` 'data') there is no
     v -> eps pass: ``eps`` returns the network output (or the guided buffer) as it is and the update (_VUpdate, sgd_v_step)
     takes the UNet's time and the two schedule tables, one launch fewer per evaluation.  With ``cfg_distilled`` in ``sk``
-    (``distilled``: a guidance-distilled student) EVERY evaluation is that one evaluation at B and ``cond_scale`` is not read"""
+    (``distilled``: a guidance-distilled student) EVERY evaluation is that one evaluation at B and ``cond_scale`` is not read.
+    With ``pag_scale`` in ``sk`` (``pag``: pag_options) the doubled evaluation runs on the perturbed-attention engine -- second
+    half: the same network, the chosen layers' attention map the identity -- and is read in the cfg form (``mode`` 2) with
+    weight s (``weight``); ``cond_scale`` is not read, the guidance schedule applies unchanged"""
 
     def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
         self.fn = denoise_sample_fn
         self.kwargs = dict(kwargs)
         self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
         self.distilled = cfg_distilled_option(sk)
+        self.pag = None
+        self._pag_on = pag_scale_option(sk) > 0     # (fused_cfg reads it; the options themselves are checked below)
         self.rescale, self.interval = cfg_options(sk, self.fused_cfg())        # refused before anything is loaded or launched
+        self.pag = pag_options(sk, self.fused_cfg(), self.model)               # likewise
         self.scheduled = self.rescale > 0 or self.interval is not None
         # 'data' (sampling kwarg v_form, checked by the sampler: v_form_option): no v -> eps pass, the update reads v itself
         self.form = "data" if (sk or {}).get("parameterization", "eps") == "v" and (sk or {}).get("v_form") == "data" else "eps"
@@ -534,22 +592,38 @@ class _StepRunner:
         m, w = self.model, self.kwargs.get("cond_scale")
         if self.distilled:                          # the same step with its conditional evaluation alone, whatever the weight
             return m is not None and self.kwargs.get("p0") is None
+        if self._pag_on:                            # the doubled evaluation whatever the weight: cond_scale is not read
+            return m is not None and self.kwargs.get("p0") is None and not isinstance(w, torch.Tensor)
         if m is None or not isinstance(w, (int, float)) or self.kwargs.get("p0") is not None:
             return False
         fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else True
         return not (fast_int and w in (0, 1))
 
+    def mode(self):
+        """how the step kernels read the doubled evaluation: the model's guided form; the cfg form under PAG"""
+        return 2 if self.pag else self.model._scale_mode()
+
+    def weight(self):
+        """the guidance weight of a guided evaluation: ``cond_scale``; ``pag_scale`` under PAG"""
+        return self.pag[0] if self.pag else float(self.kwargs["cond_scale"])
+
+    def layers(self):
+        """the ``pag`` argument of the doubled evaluation's engine (UNetModelBase._engine): None without PAG"""
+        return self.pag[1] if self.pag else None
+
     def schedule(self, times):
         """(guided flag, weight) per evaluation of a scheduled trajectory (cfg_schedule)"""
-        return cfg_schedule(times, self.kwargs["cond_scale"], self.model._scale_mode(), self.interval)
+        return cfg_schedule(times, self.weight(), self.mode(), self.interval)
 
     def drop_mask(self, B, dev):
         """(whether the model reads a cond-drop mask at all, drop probabilities [2B] of the doubled batch: the conditional
-        half never, the unconditional half always)"""
+        half never, the unconditional half always -- the perturbed half of PAG never either, unless ``pag_drop_cond``; the
+        mask's uniforms are drawn all the same)"""
         if (B, dev) not in self._drop:              # formed once per trajectory, not per step
             m = self.model
             has_mask = (m._cond_width > 0) or (m._in_ch_total > m.in_channels)
-            self._drop[B, dev] = has_mask, torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), 1.0, device=dev)))
+            p1 = 0.0 if self.pag and not self.pag[2] else 1.0
+            self._drop[B, dev] = has_mask, torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), p1, device=dev)))
         return self._drop[B, dev]
 
     def cond_only_mask(self):
@@ -580,8 +654,8 @@ class _StepRunner:
             else:
                 has_mask, p = self.drop_mask(B, x.device)
                 mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc))
-                out, mode, w = eng.eps_nhwc, m._scale_mode(), float(kw["cond_scale"])
+                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc), self.layers())
+                out, mode, w = eng.eps_nhwc, self.mode(), self.weight()
                 if self.scheduled:
                     g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
                     out, mode, w = self.guide(out, mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), 0, 0.0
@@ -811,16 +885,19 @@ class _GraphedStep:
         # (a learned-variance model under an update that ignores the variance half: the engine with the C-row head)
         # (a distilled student, sampling kwarg cfg_distilled: the engine at B is the step's only one -- the 2B engine and its
         # workspace are never built)
-        eng = m._engine((1 if runner.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]))
+        # (perturbed-attention guidance: the 2B engine of its layer set)
+        eng = m._engine((1 if runner.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]),
+                        runner.layers())
         # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
         # (the data form of 'v' captures another update launch and no conversion: a third kind of entry)
         par = "eps" if runner.v is None else ("v", runner.v[0].numel()) + (("data",) if runner.form == "data" else ())
         # a scheduled step reads its weight from the device: a sweep over weights or intervals reuses one capture (a pair
         # of graphs, when an interval is requested, is one entry)
-        w = None if runner.scheduled or runner.distilled else float(kw["cond_scale"])
-        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, m._scale_mode(), sig(cond), sig(layout), par,
+        w = None if runner.scheduled or runner.distilled else runner.weight()
+        # PAG: the layer set (it chose ``eng``) and whether the perturbed half drops the condition (the mask's probabilities)
+        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, runner.mode(), sig(cond), sig(layout), par,
                (runner.rescale, runner.interval is not None), (runner.lv, runner.head(img.shape[1]), upd.native_steps),
-               runner.distilled)
+               runner.distilled, runner.pag and runner.pag[1:])
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
         if g is None:                                       # the key covers all of ``upd`` that the capture baked in
@@ -859,7 +936,7 @@ class _GraphedStep:
             self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
             eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
             self._inputs = eng._keep_inputs             # the captured launches read these buffers on every replay
-            w, mode = float(kw["cond_scale"]), m._scale_mode()
+            w, mode = runner.weight(), runner.mode()
         # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
         self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
         data = runner.form == "data"                    # the update reads v itself, at the static t, from the static tables

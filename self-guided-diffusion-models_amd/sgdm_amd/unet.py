@@ -325,17 +325,42 @@ class UNetModelBase(nn.Module):
         pass
 
     # -------------------------------------------------------------- engine
-    def _engine(self, n, h, w, prec, head=None):
+    def attention_prefixes(self):
+        """parameter prefix of every attention layer of the plan, in execution order ('middle_block.1' is the middle one)"""
+        return attention_prefixes(self._plan)
+
+    def _pag_set(self, pag, n):
+        """the ``pag`` argument of ``_engine`` checked: a sorted tuple of attention-layer prefixes of a model whose attention
+        is the self-attention block, on an even UNet batch.  ValueError before anything is built or launched"""
+        if self.KIND == "unetca_fast":
+            raise ValueError("perturbed-attention guidance is not defined for unetca_fast: its Attention_LR keys are "
+                             "[context | null | self], there is no identity map over them")
+        if getattr(self, "use_spatial_transformer", False):
+            raise ValueError("perturbed-attention guidance is not implemented for use_spatial_transformer")
+        pag = tuple(pag)
+        known = self.attention_prefixes()
+        if not pag or list(pag) != sorted(set(pag)) or any(p not in known for p in pag):
+            raise ValueError(f"pag={pag!r}: a sorted tuple of distinct attention-layer prefixes, out of {known}")
+        if n % 2:
+            raise ValueError(f"a perturbed-attention engine runs [conditional | perturbed] halves: UNet batch {n} is odd")
+        return pag
+
+    def _engine(self, n, h, w, prec, head=None, pag=None):
         """``head``: inference engines of a learned-variance model (out_channels = 2C) whose sampler ignores the variance half
         run the head conv over weight rows [0, head) only -- ``eps_nhwc`` is then [n, H, W, head].  An engine of its own:
-        the choice is part of the key (None, the default and the only training engine: every row)"""
+        the choice is part of the key (None, the default and the only training engine: every row).
+        ``pag``: perturbed-attention guidance (Ahn et al. 2024), inference only -- a sorted tuple of attention-layer prefixes
+        whose attention map is the identity on samples [n/2, n) (``_build_attn``).  Part of the key only when set."""
         dev = self._device()
         if head is not None and not 0 < head < self.out_channels:
             raise ValueError(f"head={head!r}: a proper prefix of the {self.out_channels} output channels")
         key = (n, h, w, prec) if head is None else (n, h, w, prec, head)
+        if pag is not None:
+            pag = self._pag_set(pag, n)
+            key = key + (("pag",) + pag,)
         eng = self._engines.get(key)
         if eng is None or eng.built_on.changed():                  # a tensor moved: every pointer of the program is stale
-            eng = _Engine(self, n, h, w, prec, dev, head)
+            eng = _Engine(self, n, h, w, prec, dev, head, pag)
             eng.built_on = Stale(self._all_tensors, versions=False)
             eng.built_on.mark()
             self._engines[key] = eng
@@ -360,18 +385,18 @@ class UNetModelBase(nn.Module):
         """prob_mask_like (openaimodel.py:462-463): same RNG consumption as the reference"""
         return torch.zeros((n,), device=device).float().uniform_(0, 1) < cond_drop_prob
 
-    def _run(self, x, t, cond, layout, mask, n, head=None):
+    def _run(self, x, t, cond, layout, mask, n, head=None, pag=None):
         """one UNet evaluation at UNet batch n (inputs have n_src = len(x) rows, n % n_src == 0).
-        Returns the engine (eps in eng.eps_nhwc [n, H, W, out_channels]; ``head``: _engine, inference only)."""
+        Returns the engine (eps in eng.eps_nhwc [n, H, W, out_channels]; ``head``, ``pag``: _engine, inference only)."""
         self._check_runnable(x)
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
-            assert head is None
+            assert head is None and pag is None
             from .train import forward_train      # autograd-capable path
             return forward_train(self, x, t, cond, layout, mask, n)
         B, cx, H, W = x.shape
         assert cx == self.in_channels
         prec = L.PREC_BY_NAME[self.hip_precision]
-        eng = self._engine(n, H, W, prec, head)
+        eng = self._engine(n, H, W, prec, head, pag)
         eng.run(x, t, cond, layout, mask)
         return eng
 
@@ -390,6 +415,14 @@ class UNetModelBase(nn.Module):
                                     eng.h * eng.w, _ptr(out), torch.cuda.current_stream().cuda_stream),
                 "sgd_cfg_combine")
         return out
+
+
+def attention_prefixes(plan):
+    """parameter prefix of every ("attn", ...) layer of a block plan (input, middle, output blocks), in execution order"""
+    inp, mid, out = plan
+    blocks = [(f"input_blocks.{i}", b) for i, b in enumerate(inp)] + [("middle_block", mid)] + \
+        [(f"output_blocks.{i}", b) for i, b in enumerate(out)]
+    return [f"{prefix}.{j}" for prefix, blk in blocks for j, layer in enumerate(blk) if layer[0] == "attn"]
 
 
 def device_cus(dev):
@@ -416,9 +449,10 @@ def grad_health(dev):
 class _Engine:
     """static launch program + workspace for one (UNet batch, H, W, precision)"""
 
-    def __init__(self, model, n, h, w, prec, dev, head=None):
+    def __init__(self, model, n, h, w, prec, dev, head=None, pag=None):
         self.m, self.n, self.h, self.w, self.prec, self.dev = model, n, h, w, prec, dev
         self.head = head          # UNetModelBase._engine: the head conv's rows [0, head) only (None: all of them)
+        self.pag = frozenset(pag or ())     # attention layers whose map is the identity on samples [n/2, n); inference only
         self.lib = L.load()
         self.prog = _Program()
         self.packed = []
@@ -920,6 +954,7 @@ class _Engine:
         the SAME buffers on every replay, so a caller that replays must update them in place."""
         m, n = self.m, self.n
         stream = torch.cuda.current_stream().cuda_stream
+        assert not (train and self.pag), "a perturbed-attention engine is inference only"
         self.poll_health()
         self.prog = self.program(train)
         self.refresh(stream, train)
@@ -1226,9 +1261,16 @@ class UNetModel(UNetModelBase):
         lse = eng.buf(n, heads, T)                         # softmax statistics kept for the backward
         # head stride, k / v offsets of the (padded) layout; scale = (d^-1/4)^2 applied to q.k
         hs, ko, vo = (dp, inner, 2 * inner) if new_order else (3 * dp, dp, 2 * dp)
+        # perturbed-attention guidance (engine argument ``pag``): the core over the conditional samples [0, n/2) alone; on the
+        # perturbed samples [n/2, n) the attention map is the identity, i.e. att = v, a gather with the core's strides
+        nc = n // 2 if p in eng.pag else n
         eng.prog.add(p + ".attn", eng.attention_fn(), _ptr(qkv), 3 * inner, hs,
                      C.c_void_p(qkv.data_ptr() + 4 * ko), C.c_void_p(qkv.data_ptr() + 4 * vo), 3 * inner, hs,
-                     n, heads, T, T, dp, 1.0 / math.sqrt(d), _ptr(att), inner, _ptr(lse))
+                     nc, heads, T, T, dp, 1.0 / math.sqrt(d), _ptr(att), inner, _ptr(lse))
+        if nc != n:
+            eng.prog.add(p + ".attn_identity", eng.lib.sgd_attention_identity,
+                         C.c_void_p(qkv.data_ptr() + 4 * (nc * T * 3 * inner + vo)), 3 * inner, hs, n - nc, heads, T, dp,
+                         C.c_void_p(att.data_ptr() + 4 * nc * T * inner), inner)
         y = eng.buf(n, hh, ww, ch)
         ap = eng.igemm(p + ".proj_out", att, inner, y, ch, eng.pack([p + ".proj_out.weight"], 1, pad("out")), m=n * T,
                        rows_per_n=T, bias=p + ".proj_out.bias", res=t, stats=True)
