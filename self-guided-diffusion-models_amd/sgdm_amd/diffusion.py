@@ -52,12 +52,16 @@ import copy
 import os
 import warnings
 from functools import partial
+from typing import NamedTuple
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib as L
+from .sampling_plan import (LV_NATIVE_REFUSED, V_FORM_SAMPLERS, SamplingPlan, cfg_distilled_option, cfg_options,  # noqa: F401
+                            cfg_schedule, lv_native_option, native_steps_option, pag_options, pag_scale_option, resolve_plan,
+                            v_form_option)
 from .unet import UNetModelBase, _cfg_eval, _ptr
 
 
@@ -293,17 +297,38 @@ def _unet_of(fn):
     return None
 
 
+def _model_behind(denoise_sample_fn):
+    """the drop-in UNet a denoise function evaluates (``LatentDiffusion.set_denoise_fn`` wraps it once), else None"""
+    return _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _v_tables(sk, dev):
-    """(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod) as fp32 device tables when the sampling kwargs say
-    parameterization='v', else None ('eps', the default of a direct sampler call, and 'x0' convert nothing).
+class _Read(NamedTuple):
+    """how a step kernel reads a network output: the buffer, the guided form to apply (``mode`` 0: none, it is guided
+    already; 1 imagen, 2 cfg over the two halves of a doubled evaluation) with weight ``w``, and its layout -- ``b`` samples of
+    ``c`` channels, [b, hw, c]; a guided NCHW tensor is "one channel" over b = B * C planes"""
+    buf: object
+    mode: int
+    w: float
+    b: int
+    c: int
+
+    @classmethod
+    def guided(cls, buf, b, c):
+        return cls(buf, 0, 0.0, b, c)
+
+
+def _v_tables(sk, dev, par=None):
+    """(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod) as fp32 device tables when the parameterization (``par``: the
+    plan's; None: as the sampling kwargs say) is 'v', else None ('eps', the default of a direct sampler call, and 'x0' convert
+    nothing).
     ``p_sample_loop`` hands over the training schedule's buffers; a direct caller that passes only ``alphas_cumprod`` gets
     the square roots formed from it in double and rounded once (the fp32 ``alphas_cumprod`` resolves 1 - ac to ~6e-4 at
     t = 0, where the schedule's own table was rounded from float64: pass the tables where that matters)"""
-    par = (sk or {}).get("parameterization", "eps")
+    par = (sk or {}).get("parameterization", "eps") if par is None else par
     if par != "v":
         if par not in ("eps", "x0"):
             raise NotImplementedError(f"parameterization '{par}'")
@@ -313,141 +338,6 @@ def _v_tables(sk, dev):
         ac = sk["alphas_cumprod"].detach().double()
         sa, s1 = ac.sqrt(), (1.0 - ac).sqrt()
     return tuple(a.detach().to(dev, torch.float32).contiguous() for a in (sa, s1))
-
-
-def cfg_options(sk, fused=True):
-    """(cfg_rescale, cfg_interval) of the sampling kwargs: phi in [0, 1] (0: off) and ``(t_lo, t_hi)`` in training timesteps,
-    inclusive (None: guidance on every evaluation).  ValueError for a value out of range and, with an option set, for a step
-    that is not the fused-CFG one (``fused``: _StepRunner.fused_cfg()) -- the guide pass works on the two halves of the doubled
-    evaluation.  The sampling kwarg ``cfg_distilled`` (a guidance-distilled student: every evaluation the conditional one at
-    B) is refused with either option -- there is no second half to guide or rescale with --, with the learned-variance
-    'native' update and on a step that is not the drop-in UNet's.  Pure host code: no device, no library."""
-    sk = sk or {}
-    if cfg_distilled_option(sk):
-        if sk.get("cfg_interval") is not None or sk.get("cfg_rescale", 0) != 0:
-            raise ValueError("cfg_distilled with cfg_interval / cfg_rescale: a distilled student has one (conditional) "
-                             "evaluation per step, there is no guidance to schedule or rescale")
-        if sk.get("lv_native", False):
-            raise ValueError("cfg_distilled with the learned-variance 'native' update: distillation of learned-variance "
-                             "models is not implemented")
-        if not fused:
-            raise ValueError("cfg_distilled needs the drop-in UNet's forward_with_cond_scale as denoise_sample_fn (and no p0): "
-                             "a generic denoise_sample_fn guides inside the call")
-        return 0.0, None
-    phi, iv = sk.get("cfg_rescale", 0), sk.get("cfg_interval")
-    if isinstance(phi, bool) or not isinstance(phi, (int, float)) or not 0.0 <= phi <= 1.0:       # (NaN fails the comparison)
-        raise ValueError(f"cfg_rescale={phi!r}: a number in [0, 1]")
-    if iv is not None:
-        ok = isinstance(iv, (tuple, list)) and len(iv) == 2 and all(
-            isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in iv)
-        if not ok or iv[0] > iv[1]:
-            raise ValueError(f"cfg_interval={iv!r}: (t_lo, t_hi), two ints in training timesteps with t_lo <= t_hi")
-        iv = (int(iv[0]), int(iv[1]))
-    if (phi > 0 or iv is not None) and not fused:
-        raise ValueError("cfg_rescale / cfg_interval need the fused-CFG step: the drop-in UNet's forward_with_cond_scale, a "
-                         "numeric cond_scale that is not its single-evaluation 0 / 1 shortcut, and no p0")
-    return float(phi), iv
-
-
-def cfg_distilled_option(sk):
-    """the sampling kwarg ``cfg_distilled`` (default False), a bool.  Pure host code."""
-    on = (sk or {}).get("cfg_distilled", False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError(f"cfg_distilled={on!r} (True or False)")
-    return bool(on)
-
-
-def pag_scale_option(sk):
-    """the sampling kwarg ``pag_scale`` (perturbed-attention guidance, Ahn et al. 2024): a finite number >= 0; 0, the default,
-    is off.  ValueError for anything else (a bool included).  Pure host code."""
-    s = (sk or {}).get("pag_scale", 0)
-    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, float, np.integer, np.floating)) or not 0.0 <= s < float("inf"):
-        raise ValueError(f"pag_scale={s!r}: a finite number >= 0 (0: off)")               # (NaN fails the comparison)
-    return float(s)
-
-
-def pag_options(sk, fused=True, model=None):
-    """None (off), or ``(s, layers, drop_cond)`` of the sampling kwargs ``pag_scale`` / ``pag_layers`` / ``pag_drop_cond``:
-    perturbed-attention guidance, eps_c + s (eps_c - eps_p) with eps_p the SAME network whose self-attention map is the
-    identity in ``layers`` -- the cfg form of the step kernels with u := eps_p and w := s, whatever the model's scale_type;
-    ``cond_scale`` is not read.  ``layers``: a sorted tuple of attention-layer prefixes of ``model`` -- from 'mid' (default, the
-    middle block's attention), 'all', or a list of prefixes.  ``drop_cond`` (default False): the perturbed half also drops the
-    condition, drop probabilities (0, 1) as for CFG instead of (0, 0).  ValueError, before anything is loaded or launched, for
-    a value out of range, an unknown prefix or a selection of nothing, ``pag_layers`` / ``pag_drop_cond`` without
-    ``pag_scale > 0``, ``cfg_distilled`` (one evaluation per step: no second half), a step that is not the drop-in UNet's fused
-    one (``fused``: _StepRunner.fused_cfg() -- a generic denoise_sample_fn, p0, a tensor cond_scale) and a model whose
-    attention is not the self-attention block (unetca_fast, use_spatial_transformer).  Pure host code: no device, no library."""
-    sk = sk or {}
-    s = pag_scale_option(sk)
-    layers, drop = sk.get("pag_layers"), sk.get("pag_drop_cond")
-    if s == 0:
-        if layers is not None or drop is not None:
-            raise ValueError("pag_layers / pag_drop_cond without pag_scale > 0")
-        return None
-    if cfg_distilled_option(sk):
-        raise ValueError("pag_scale with cfg_distilled: a distilled student has one (conditional) evaluation per step, there "
-                         "is no perturbed half to guide with")
-    if not fused or model is None:
-        raise ValueError("pag_scale needs the fused step: the drop-in UNet's forward_with_cond_scale as denoise_sample_fn, no "
-                         "p0 and no tensor cond_scale")
-    if drop is not None and not isinstance(drop, (bool, np.bool_)):
-        raise ValueError(f"pag_drop_cond={drop!r} (True or False)")
-    known = model.attention_prefixes()
-    if layers is None or (isinstance(layers, str) and layers == "mid"):
-        want = [p for p in known if p.startswith("middle_block.")]
-    elif isinstance(layers, str) and layers == "all":
-        want = known
-    elif isinstance(layers, (list, tuple)) and all(isinstance(p, str) for p in layers):
-        want = list(layers)
-    else:
-        raise ValueError(f"pag_layers={layers!r}: 'mid', 'all' or a list of attention-layer prefixes ({known})")
-    # the engine's own check of its ``pag`` argument (2: any even UNet batch): the model kind, unknown prefixes, an empty set
-    return s, model._pag_set(tuple(sorted(set(want))), 2), bool(drop)
-
-
-V_FORM_SAMPLERS = ("native", "ddim", "dpmsolver")
-
-
-def v_form_option(sk, method, ac_visited=None, par=None):
-    """'eps' | 'data': the sampling kwarg ``v_form`` of a 'v' trajectory.  'eps' (default): the network output is changed to
-    eps (sgd_v_to_eps) and the sampler's own kernel forms x0 = (x - s1 eps) / sa.  'data': ONE launch (sgd_v_step) forms
-    x0 = sa x - s1 v and eps = sa v + s1 x and performs the update from them, finite at sa = 0.  ValueError, before anything
-    is loaded or launched, for 'data' with a parameterization other than 'v' (``par``: the one in force when the kwargs leave
-    it to the schedule), with dynamic thresholding, or on 'plms' / 'pndm' (multistep methods on eps; 'pndm' keeps a schedule of
-    its own); and for an eps-form trajectory that visits an ``alphas_cumprod`` of 0 (``ac_visited``: the table entries of the
-    visited times), where x0 = 0 / 0.  Pure host code: no device, no library."""
-    sk = sk or {}
-    form = sk.get("v_form", "eps")
-    if form not in ("eps", "data"):
-        raise ValueError(f"v_form={form!r} ('eps' or 'data')")
-    if form == "data":
-        par = sk.get("parameterization", "eps") if par is None else par
-        if par != "v":
-            raise ValueError(f"v_form='data' reads the network output as v: parameterization '{par}' has no data form")
-        if sk.get("dtp", 1) < 1.0:
-            raise ValueError("v_form='data': dynamic thresholding (dtp < 1) is not implemented on the data form")
-        if method not in V_FORM_SAMPLERS:
-            raise ValueError(f"v_form='data' is implemented for {', '.join(V_FORM_SAMPLERS)}; '{method}' is a multistep method "
-                             "on eps")
-    elif ac_visited is not None and bool((np.asarray(ac_visited, dtype=np.float64) == 0.0).any()):
-        raise ValueError(f"'{method}' on the eps form visits a time whose alphas_cumprod is 0 (a zero-terminal-SNR schedule): "
-                         "x0 = (x - s1 eps) / sa is 0 / 0 there.  Use parameterization='v' with v_form='data' (native, ddim, "
-                         "dpmsolver), or a timestep spacing that does not visit it")
-    return form
-
-
-def native_steps_option(sk, method, T):
-    """None | K: the sampling kwarg ``native_steps`` of the 'native' sampler, a strided ancestral chain over K of the T
-    training times (2 <= K <= T).  ValueError, before anything is loaded or launched, on another sampler or out of range.
-    Pure host code."""
-    K = (sk or {}).get("native_steps")
-    if K is None:
-        return None
-    if method != "native":
-        raise ValueError(f"native_steps strides the 'native' sampler; '{method}' takes num_timesteps")
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 2 <= K <= T:
-        raise ValueError(f"native_steps={K!r}: an int, 2 .. {T}")
-    return int(K)
 
 
 def native_times(K, T):
@@ -502,75 +392,29 @@ def native_rows(ac, kind, parameterization, temperature):
     return torch.tensor(tab, dtype=torch.float64).float(), beta
 
 
-LV_NATIVE_REFUSED = ("dtp", "noise_dropout", "cfg_interval", "cfg_rescale", "v_form")
-
-
-def lv_native_option(sk):
-    """the 'native' sampler of a learned-variance model (update kind 'lv_native', sgd_ddpm_lv_step) refuses what its one
-    launch does not implement -- dynamic thresholding, noise dropout, the guidance schedule, the data form of 'v' (its row
-    already avoids dividing by sqrt(alphas_cumprod) for 'v') -- with ValueError, before anything is loaded or launched"""
-    sk = sk or {}
-    if sk.get("dtp", 1) < 1.0:
-        raise ValueError("learn_sigma 'native': dynamic thresholding (dtp < 1) is not implemented")
-    if sk.get("noise_dropout", 0) > 0:
-        raise ValueError("learn_sigma 'native': noise_dropout is not implemented")
-    if sk.get("cfg_interval") is not None or sk.get("cfg_rescale", 0) != 0:
-        raise ValueError("learn_sigma 'native': cfg_interval / cfg_rescale are not implemented")
-    if sk.get("v_form", "eps") == "data":
-        raise ValueError("learn_sigma 'native': v_form='data' is not needed, the row of a 'v' model never divides by "
-                         "sqrt(alphas_cumprod)")
-
-
-def cfg_schedule(times, cond_scale, scale_mode, interval=None):
-    """per UNet EVALUATION of a trajectory (``times``: its time argument, one entry per evaluation -- PNDM's list repeats
-    times): (guided, weight).  An evaluation is guided when ``t_lo <= t <= t_hi`` (``interval`` None: always) and then has
-    weight ``cond_scale``; the others take the conditional prediction alone, which is weight 1 of the imagen form
-    (``scale_mode`` 1, _scale_mode()) and weight 0 of the cfg form (2).  Pure host code."""
-    if scale_mode not in (1, 2):
-        raise ValueError(f"scale_mode={scale_mode!r} (1: imagen, 2: cfg)")
-    off = 1.0 if scale_mode == 1 else 0.0
-    guided = [interval is None or interval[0] <= int(t) <= interval[1] for t in times]
-    return guided, [float(cond_scale) if g else off for g in guided]
-
-
 class _StepRunner:
-    """one sampling step = UNet(2B) + one fused update kernel (+ the v -> eps pass between them when ``sk`` says
-    parameterization='v').  With ``cfg_rescale`` / ``cfg_interval`` in ``sk`` (``scheduled``) a guided evaluation puts the
-    guide pass (sgd_cfg_guide) behind the UNet and everything after it reads the guided buffer with mode 0; an evaluation
-    outside the interval is ONE UNet evaluation at B, nothing dropped.  On the data form of 'v' (``form`` 'data') there is no
-    v -> eps pass: ``eps`` returns the network output (or the guided buffer) as it is and the update (_VUpdate, sgd_v_step)
-    takes the UNet's time and the two schedule tables, one launch fewer per evaluation.  With ``cfg_distilled`` in ``sk``
-    (``distilled``: a guidance-distilled student) EVERY evaluation is that one evaluation at B and ``cond_scale`` is not read.
-    With ``pag_scale`` in ``sk`` (``pag``: pag_options) the doubled evaluation runs on the perturbed-attention engine -- second
-    half: the same network, the chosen layers' attention map the identity -- and is read in the cfg form (``mode`` 2) with
-    weight s (``weight``); ``cond_scale`` is not read, the guidance schedule applies unchanged"""
+    """one sampling step's evaluation = UNet (at 2B on the fused path, at B where the plan says cond-only) + the guide pass
+    and the v -> eps pass where the plan puts them, described to the update kernel by a ``_Read``.  What the trajectory was
+    asked to do is ``plan`` (SamplingPlan: resolved here with the defaults of a bare step when the sampler hands none over);
+    the runner owns the device side: the library handle, the 'v' schedule tables (``v``) and the drop-mask cache."""
 
-    def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None):
+    def __init__(self, denoise_sample_fn, kwargs, sk=None, dev=None, plan=None):
         self.fn = denoise_sample_fn
         self.kwargs = dict(kwargs)
-        self.model = _unet_of(getattr(denoise_sample_fn, "_sgdm_inner", denoise_sample_fn))
-        self.distilled = cfg_distilled_option(sk)
-        self.pag = None
-        self._pag_on = pag_scale_option(sk) > 0     # (fused_cfg reads it; the options themselves are checked below)
-        self.rescale, self.interval = cfg_options(sk, self.fused_cfg())        # refused before anything is loaded or launched
-        self.pag = pag_options(sk, self.fused_cfg(), self.model)               # likewise
-        self.scheduled = self.rescale > 0 or self.interval is not None
-        # 'data' (sampling kwarg v_form, checked by the sampler: v_form_option): no v -> eps pass, the update reads v itself
-        self.form = "data" if (sk or {}).get("parameterization", "eps") == "v" and (sk or {}).get("v_form") == "data" else "eps"
-        # a learned-variance model's output is 2C wide.  ``lv`` (kwarg lv_native, set by the 'native' sampler of such a
-        # model): the update reads the RAW output, both halves, whatever the parameterization; every other update ignores the
-        # variance half and must not pay for it: the engine's head conv runs over weight rows [0, C) (``head``).  Which of
-        # the two it is follows from the model's width, not from a kwarg a direct caller could forget.
-        self.lv = bool((sk or {}).get("lv_native", False))
+        self.model = _model_behind(denoise_sample_fn)
+        # (every refusal is raised by the resolver: before anything is loaded or launched)
+        self.plan = resolve_plan(sk, None, self.model, self.kwargs) if plan is None else plan
         self.lib = L.load()
         self._drop = {}
-        self.v = None if self.lv else _v_tables(sk, dev)
+        self.v = None if self.plan.lv else _v_tables(sk, dev, self.plan.par)
+
+    form = property(lambda self: self.plan.form)
 
     def width(self, out_c, Cc):
         """what a step does with a network output of ``out_c`` channels for an image of ``Cc``: 'raw' (the learned-variance
         update reads all 2C), 'narrow' (2C wide, the update reads the mean half only) or 'plain'.  ValueError for any other
         width: the step kernels would read the output with the wrong stride"""
-        if self.lv:
+        if self.plan.lv:
             if out_c != 2 * Cc:
                 raise ValueError(f"the learned-variance 'native' update needs a network output of {2 * Cc} channels, not {out_c}")
             return "raw"
@@ -586,35 +430,6 @@ class _StepRunner:
         mean rows alone when the model is 2C wide and the update ignores the variance half"""
         return Cc if self.model is not None and self.width(self.model.out_channels, Cc) == "narrow" else None
 
-    def fused_cfg(self):
-        """whether a step takes the batch-doubled evaluation whose guided score is formed inside the step kernel: the
-        drop-in UNet, a numeric guidance weight that is not the model kind's single-evaluation 0 / 1 shortcut, no ``p0``"""
-        m, w = self.model, self.kwargs.get("cond_scale")
-        if self.distilled:                          # the same step with its conditional evaluation alone, whatever the weight
-            return m is not None and self.kwargs.get("p0") is None
-        if self._pag_on:                            # the doubled evaluation whatever the weight: cond_scale is not read
-            return m is not None and self.kwargs.get("p0") is None and not isinstance(w, torch.Tensor)
-        if m is None or not isinstance(w, (int, float)) or self.kwargs.get("p0") is not None:
-            return False
-        fast_int = isinstance(w, int) if m.KIND == "unetca_fast" else True
-        return not (fast_int and w in (0, 1))
-
-    def mode(self):
-        """how the step kernels read the doubled evaluation: the model's guided form; the cfg form under PAG"""
-        return 2 if self.pag else self.model._scale_mode()
-
-    def weight(self):
-        """the guidance weight of a guided evaluation: ``cond_scale``; ``pag_scale`` under PAG"""
-        return self.pag[0] if self.pag else float(self.kwargs["cond_scale"])
-
-    def layers(self):
-        """the ``pag`` argument of the doubled evaluation's engine (UNetModelBase._engine): None without PAG"""
-        return self.pag[1] if self.pag else None
-
-    def schedule(self, times):
-        """(guided flag, weight) per evaluation of a scheduled trajectory (cfg_schedule)"""
-        return cfg_schedule(times, self.weight(), self.mode(), self.interval)
-
     def drop_mask(self, B, dev):
         """(whether the model reads a cond-drop mask at all, drop probabilities [2B] of the doubled batch: the conditional
         half never, the unconditional half always -- the perturbed half of PAG never either, unless ``pag_drop_cond``; the
@@ -622,7 +437,8 @@ class _StepRunner:
         if (B, dev) not in self._drop:              # formed once per trajectory, not per step
             m = self.model
             has_mask = (m._cond_width > 0) or (m._in_ch_total > m.in_channels)
-            p1 = 0.0 if self.pag and not self.pag[2] else 1.0
+            pag = self.plan.pag
+            p1 = 0.0 if pag and not pag[2] else 1.0
             self._drop[B, dev] = has_mask, torch.cat((torch.full((B,), 0.0, device=dev), torch.full((B,), p1, device=dev)))
         return self._drop[B, dev]
 
@@ -636,45 +452,44 @@ class _StepRunner:
 
     def guide(self, out, mode, w_dev, B, Cc, hw, g, st):
         """the guide pass: ``out`` [2B, hw, C] -> ``g`` [B, hw, C], weight from the device float ``w_dev``"""
-        L.check(self.lib.sgd_cfg_guide(_ptr(out), mode, _ptr(w_dev), self.rescale, B, Cc, hw, _ptr(g), st), "sgd_cfg_guide")
+        L.check(self.lib.sgd_cfg_guide(_ptr(out), mode, _ptr(w_dev), self.plan.rescale, B, Cc, hw, _ptr(g), st), "sgd_cfg_guide")
         return g
 
     def eps(self, x, t, guided=True, w_dev=None):
-        """returns (eps tensor/engine buffer, cfg_mode, w, b, c) describing how the step kernel reads it.  A scheduled
-        trajectory's step object says whether this evaluation is ``guided`` and hands over its weight as a device float"""
+        """the evaluation at (x, t) as the ``_Read`` of the step kernel.  A scheduled trajectory's step object says whether
+        this evaluation is ``guided`` and hands over its weight as a device float"""
         B, Cc = x.shape[0], x.shape[1]
-        m = self.model
-        if self.fused_cfg():
+        m, plan = self.model, self.plan
+        if plan.fused:
             kw = self.kwargs
-            if self.distilled or (self.scheduled and not guided):
+            if plan.distilled or (plan.scheduled and not guided):
                 # the conditional prediction alone: one evaluation at B, RNG consumed as forward(cond_drop_prob=p0) does
                 mask = m._draw_mask(B, 0.0, x.device) if self.cond_only_mask() else None
-                eng, mode, w = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B, self.head(Cc)), 0, 0.0
-                out = eng.eps_nhwc
+                read = _Read.guided(m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B, self.head(Cc)).eps_nhwc, B, Cc)
             else:
                 has_mask, p = self.drop_mask(B, x.device)
                 mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc), self.layers())
-                out, mode, w = eng.eps_nhwc, self.mode(), self.weight()
-                if self.scheduled:
+                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc), plan.layers)
+                read = _Read(eng.eps_nhwc, plan.mode, plan.weight, B, Cc)
+                if plan.scheduled:
                     g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
-                    out, mode, w = self.guide(out, mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), 0, 0.0
-            if self.v is None or self.form == "data":       # the data-form update reads v itself, with this mode and weight
-                return out, mode, w, B, Cc
+                    read = _Read.guided(self.guide(read.buf, read.mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), B, Cc)
+            if self.v is None or plan.form == "data":       # the data-form update reads v itself, with this mode and weight
+                return read
             e = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
-            return self.v_to_eps(x, out, t, mode, w, B, Cc, e, _stream()), 0, 0.0, B, Cc
+            return _Read.guided(self.v_to_eps(x, read.buf, t, read.mode, read.w, B, Cc, e, _stream()), B, Cc)
         e = self.fn(x, t, **self.kwargs).contiguous()       # generic path: guided output, NCHW
         width = self.width(e.shape[1], Cc)
         if width == "raw":                                  # [B, 2C, H, W] re-laid as the raw output [B, hw, 2C]; not hot
-            return e.float().reshape(B, 2 * Cc, -1).permute(0, 2, 1).contiguous(), 0, 0.0, B, Cc
+            return _Read.guided(e.float().reshape(B, 2 * Cc, -1).permute(0, 2, 1).contiguous(), B, Cc)
         if width == "narrow":
             e = e[:, :Cc].contiguous()                      # the variance half is ignored
-        if self.form == "data":
-            return e.float(), 0, 0.0, B * Cc, 1
+        if plan.form == "data":
+            return _Read.guided(e.float(), B * Cc, 1)
         if self.v is not None:
             # B*C one-channel planes, one time per plane
             e = self.v_to_eps(x, e.float(), t.repeat_interleave(Cc), 0, 0.0, B * Cc, 1, torch.empty_like(x), _stream())
-        return e, 0, 0.0, B * Cc, 1
+        return _Read.guided(e, B * Cc, 1)
 
     def v_to_eps(self, x, v, t, mode, w, b, c, out, st, tables=None):
         """parameterization 'v': the network output ``v`` (laid out as the step kernels read an eps with ``mode``) guided and
@@ -710,20 +525,27 @@ def _quantile_rank(dtp, count):
 class _Update:
     """One sampler's update kernel, as both step classes below drive it: the ONE place the kernel is launched from, the state
     buffers it keeps between launches (``alloc``), the layout of a row of the trajectory's table (``COEF``) and what it
-    honours of the sampling kwargs -- ``NOISE``: it reads a ``z`` (drawn per step, at eta = 0 too); ``EXTRAS``: noise dropout
-    and dynamic thresholding (dtp < 1), which only the eager step runs.  ``launch`` reads its row from DEVICE memory; an
-    update with ``NOISE`` also takes ``z`` and ``want_x0`` (the others have no noise and no optional output)."""
+    honours of the plan -- ``NOISE``: it reads a ``z`` (drawn per step, at eta = 0 too); ``EXTRAS``: noise dropout and dynamic
+    thresholding (dtp < 1), which only the eager step runs.  ``launch`` has ONE signature: the image ``x``, the ``_Read`` of
+    the network output, the address of its row in DEVICE memory, ``x_out``, and what only some kernels read -- ``z`` (None:
+    the update's own buffer) and ``want_x0`` (``NOISE``), the UNet's time ``t`` and the two schedule ``tables`` (_VUpdate)."""
 
     COEF = None                 # (words, dtype) of one row: every update states its own
     NOISE = False
     EXTRAS = False
     x0 = None                   # clipped x0 prediction of the last launch (snapshot steps clone it), where there is one
-    native_steps = None         # 'native' only: the sampling kwarg of a strided chain (part of a captured step's cache key)
 
-    def __init__(self, kind, sk, clip, temperature=1.0):
-        self.lib, self.kind, self.clip, self.temperature = L.load(), kind, clip, float(temperature)
-        self.noise_dropout = sk.get("noise_dropout", 0) if self.EXTRAS else 0
-        self.dtp = sk.get("dtp", 1) if self.EXTRAS else 1
+    def __init__(self, kind, plan, temperature=1.0, noise=None):
+        self.lib, self.kind, self.clip, self.temperature = L.load(), kind, plan.clip, float(temperature)
+        self.native_steps = plan.native_steps
+        if noise is not None:
+            self.NOISE = bool(noise)
+        self.noise_dropout = plan.noise_dropout if self.EXTRAS or noise else 0
+        self.dtp = plan.dtp if self.EXTRAS else 1
+
+    def capture_key(self):
+        """what a captured step bakes in of the update (its kernel arguments by value, and whose rows it reads)"""
+        return self.kind, self.clip, self.temperature, self.native_steps
 
 
 class _DDUpdate(_Update):
@@ -752,8 +574,9 @@ class _DDUpdate(_Update):
             z = noise
         return torch.nn.functional.dropout(z, p=self.noise_dropout) if self.noise_dropout > 0. else z
 
-    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True):
+    def launch(self, st, x, read, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
         lib, ddpm, dyn = self.lib, self.kind == "ddpm", None
+        eps, mode, w, b, c = read
         if self.rank is not None:
             # the quantile is per SAMPLE: the one-channel planes of a guided eps are re-laid as [B, hw, C] (the layout is
             # told by (b, c), not by the mode: the converted eps of parameterization 'v' is [B, hw, C] with mode 0)
@@ -783,7 +606,8 @@ class _PNDMUpdate(_Update):
         self.acc, self.base = torch.empty_like(img), torch.empty_like(img)
         self.ring = torch.empty((3,) + tuple(img.shape), dtype=img.dtype, device=img.device)
 
-    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out):
+    def launch(self, st, x, read, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+        eps, mode, w, b, c = read
         L.check(self.lib.sgd_pndm_step(_ptr(x), _ptr(eps), mode, w, row_dev, _ptr(self.acc), _ptr(self.base),
                                        _ptr(self.ring), b, c, hw, _ptr(x_out), st), "sgd_pndm_step")
 
@@ -798,7 +622,8 @@ class _DPMUpdate(_Update):
     def alloc(self, img):
         self.x0 = torch.empty_like(img)
 
-    def launch(self, st, x, eps, mode, w, b, c, hw, row_dev, x_out):
+    def launch(self, st, x, read, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+        eps, mode, w, b, c = read
         L.check(self.lib.sgd_dpmpp_step(_ptr(x), _ptr(eps), mode, w, row_dev, _ptr(self.x0), self.clip, b, c, hw,
                                         _ptr(x_out), st), "sgd_dpmpp_step")
 
@@ -808,15 +633,11 @@ class _VUpdate(_Update):
     'v_dpmsolver').  A row is one ``sgd_vstep_row`` (include/sgdm_hip.h); it carries everything the samplers' own kernels take
     by value (the DDIM temperature is folded into ``kz``), so the kind only says whose rows these are.  ``x0`` is the clipped
     data prediction the snapshots log and the history a 'dpmsolver' row with ``kh != 0`` reads; a trajectory's first row has
-    ``kh == 0``.  ``launch`` also takes the UNet's time ``t`` [B] and the two schedule tables.  ``noise``: the sampler draws a
-    ``z`` per step ('native', 'ddim': in the reference's order, at eta = 0 too) and honours noise dropout, eager only."""
+    ``kh == 0``.  The one update that reads the UNet's time ``t`` [B] and the two schedule tables.  ``noise`` (constructor):
+    the sampler draws a ``z`` per step ('native', 'ddim': in the reference's order, at eta = 0 too) and honours noise dropout,
+    eager only."""
 
     COEF = (8, torch.float32)
-
-    def __init__(self, kind, sk, clip, noise):
-        super().__init__(kind, sk, clip)
-        self.NOISE = bool(noise)
-        self.noise_dropout = sk.get("noise_dropout", 0) if noise else 0
 
     def alloc(self, img):
         self.x0 = torch.empty_like(img)
@@ -824,7 +645,8 @@ class _VUpdate(_Update):
 
     draw = _DDUpdate.draw
 
-    def launch(self, st, x, v, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+    def launch(self, st, x, read, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+        v, mode, w, b, c = read
         if t.numel() != b:                                  # b = B * C one-channel planes (generic path): one time per plane
             t = t.repeat_interleave(b // t.numel())
         sa, s1 = tables
@@ -833,7 +655,7 @@ class _VUpdate(_Update):
 
 
 class _LVUpdate(_Update):
-    """``sgd_ddpm_lv_step`` (kind 'lv_native'): the ancestral update of a learned-variance model.  ``eps`` is the RAW network
+    """``sgd_ddpm_lv_step`` (kind 'lv_native'): the ancestral update of a learned-variance model.  It reads the RAW network
     output, 2C channels wide ([2B | B, hw, 2C]): the kernel guides the mean channels and reads the variance channels from
     the conditional half.  A row is one ``sgd_lvstep_row`` (include/sgdm_hip.h); the parameterization lives in its (k0, k1),
     the per-step temperature in its kz.  Neither noise dropout nor dynamic thresholding (``lv_native_option`` refuses them)."""
@@ -846,7 +668,8 @@ class _LVUpdate(_Update):
 
     draw = _DDUpdate.draw
 
-    def launch(self, st, x, out, mode, w, b, c, hw, row_dev, x_out, z=None, want_x0=True):
+    def launch(self, st, x, read, hw, row_dev, x_out, z=None, want_x0=True, t=None, tables=None):
+        out, mode, w, b, c = read
         L.check(self.lib.sgd_ddpm_lv_step(_ptr(x), _ptr(out), _ptr(self.z if z is None else z), mode, w, row_dev, self.clip,
                                           b, c, hw, _ptr(x_out), _ptr(self.x0 if want_x0 else None), st), "sgd_ddpm_lv_step")
 
@@ -878,26 +701,18 @@ class _GraphedStep:
     def get(cls, runner, img, upd, times, tab):
         """the captured step for this (model, batch, resolution, precision, guidance, sampler) -- built on first use and
         kept on the model, so later trajectories of the same configuration only refresh the static input buffers"""
-        m, kw = runner.model, runner.kwargs
+        m, kw, plan = runner.model, runner.kwargs, runner.plan
         cond, layout = kw.get("cond"), kw.get("layout")
         sig = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         prec = L.PREC_BY_NAME[m.hip_precision]
-        # (a learned-variance model under an update that ignores the variance half: the engine with the C-row head)
-        # (a distilled student, sampling kwarg cfg_distilled: the engine at B is the step's only one -- the 2B engine and its
-        # workspace are never built)
-        # (perturbed-attention guidance: the 2B engine of its layer set)
-        eng = m._engine((1 if runner.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, runner.head(img.shape[1]),
-                        runner.layers())
-        # parameterization 'v' captures one more launch (and reads tables of this length): a graph of its own
-        # (the data form of 'v' captures another update launch and no conversion: a third kind of entry)
-        par = "eps" if runner.v is None else ("v", runner.v[0].numel()) + (("data",) if runner.form == "data" else ())
-        # a scheduled step reads its weight from the device: a sweep over weights or intervals reuses one capture (a pair
-        # of graphs, when an interval is requested, is one entry)
-        w = None if runner.scheduled or runner.distilled else runner.weight()
-        # PAG: the layer set (it chose ``eng``) and whether the perturbed half drops the condition (the mask's probabilities)
-        key = (id(eng), tuple(img.shape), upd.kind, upd.clip, upd.temperature, w, runner.mode(), sig(cond), sig(layout), par,
-               (runner.rescale, runner.interval is not None), (runner.lv, runner.head(img.shape[1]), upd.native_steps),
-               runner.distilled, runner.pag and runner.pag[1:])
+        # the engine of the doubled evaluation: with the C-row head where a learned-variance model's update ignores the
+        # variance half, of the plan's PAG layer set; a distilled student's is the engine at B, its only one (the 2B engine
+        # and its workspace are never built)
+        head = runner.head(img.shape[1])
+        eng = m._engine((1 if plan.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, head, plan.layers)
+        # what only this place knows, then what the plan and the update say the capture bakes in of them
+        key = (id(eng), tuple(img.shape), sig(cond), sig(layout), None if runner.v is None else runner.v[0].numel(), head,
+               plan.capture_key(), upd.capture_key())
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
         if g is None:                                       # the key covers all of ``upd`` that the capture baked in
@@ -928,7 +743,8 @@ class _GraphedStep:
         self.cond = None if c0 is None else (c0.detach().clone() if c0.dtype == torch.int64 else c0.detach().float().clone()).contiguous()
         self.layout = None if l0 is None else (l0.detach().clone() if l0.dtype in (torch.uint8, torch.int32, torch.int64)
                                                else l0.detach().float().clone()).contiguous()
-        self.distilled = runner.distilled               # ``eng`` is the engine at B and ``graph1`` the only graph
+        plan = runner.plan
+        self.distilled = plan.distilled                 # ``eng`` is the engine at B and ``graph1`` the only graph
         img = self.img
         if not self.distilled:
             self.has_mask, self.p = runner.drop_mask(B, dev)
@@ -936,37 +752,32 @@ class _GraphedStep:
             self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
             eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
             self._inputs = eng._keep_inputs             # the captured launches read these buffers on every replay
-            w, mode = runner.weight(), runner.mode()
         # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
         self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
-        data = runner.form == "data"                    # the update reads v itself, at the static t, from the static tables
-        self.veps = None if runner.v is None or data else torch.empty((B, hw, Cc), device=dev)
+        # (on the data form the update reads v itself, at the static t, from the static tables)
+        self.veps = None if runner.v is None or plan.form == "data" else torch.empty((B, hw, Cc), device=dev)
         # scheduled guidance: this step's weight and the guided output
-        self.scheduled = runner.scheduled
+        self.scheduled = plan.scheduled
         self.w = torch.zeros(1, device=dev) if self.scheduled else None
         self.g = torch.empty((B, hw, Cc), device=dev) if self.scheduled else None
         self.flags = self.wtab = None
         self.replays = dict(guided=0, cond=0)
 
-        def tail(st, eps, mode, w):
-            if runner.lv:                               # the raw 2C-wide output, guided inside the update
-                return upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
-            if data:
-                return upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img, t=self.t, tables=self.v)
-            if self.v is not None:                      # v -> guided eps at this step's time; the update reads it with mode 0
-                eps, mode, w = runner.v_to_eps(img, eps, self.t, mode, w, B, Cc, self.veps, st, self.v), 0, 0.0
-            # reads ``eps`` (the UNet's output in the engine, the guided buffer or the converted eps), updates img in place
-            upd.launch(st, img, eps, mode, w, B, Cc, hw, self.coef.data_ptr(), img)
+        def tail(st, read):
+            if self.veps is not None:                   # v -> guided eps at this step's time; the update reads it with mode 0
+                read = _Read.guided(runner.v_to_eps(img, read.buf, self.t, read.mode, read.w, B, Cc, self.veps, st, self.v), B, Cc)
+            # reads the UNet's output in the engine, the guided buffer or the converted eps; updates img in place
+            upd.launch(st, img, read, hw, self.coef.data_ptr(), img, t=self.t, tables=self.v)
 
         def guided_step(st):
             eng.launch(st)
             if self.scheduled:
-                return tail(st, runner.guide(eng.eps_nhwc, mode, self.w, B, Cc, hw, self.g, st), 0, 0.0)
-            tail(st, eng.eps_nhwc, mode, w)
+                return tail(st, _Read.guided(runner.guide(eng.eps_nhwc, plan.mode, self.w, B, Cc, hw, self.g, st), B, Cc))
+            tail(st, _Read(eng.eps_nhwc, plan.mode, plan.weight, B, Cc))
 
         self.graph = None if self.distilled else self._capture(eng, guided_step, dev)
         self.eng1 = self.graph1 = self.u1 = None
-        if runner.interval is not None or self.distilled:
+        if plan.interval is not None or self.distilled:
             # the conditional prediction alone: the engine at B over the same img / t / cond / layout; its mask stays all-false
             # (``u1`` is only drawn into, to consume the RNG like the model's own single evaluation)
             eng1 = self.eng1 = eng if self.distilled else m._engine(B, img.shape[2], img.shape[3], eng.prec, runner.head(Cc))
@@ -977,7 +788,7 @@ class _GraphedStep:
 
             def cond_step(st):
                 eng1.launch(st)
-                tail(st, eng1.eps_nhwc, 0, 0.0)
+                tail(st, _Read.guided(eng1.eps_nhwc, B, Cc))
 
             self.graph1 = self._capture(eng1, cond_step, dev)
 
@@ -1015,7 +826,7 @@ class _GraphedStep:
                 dst.copy_(src)
         self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
         if self.scheduled:
-            self.flags, ws = runner.schedule(times)
+            self.flags, ws = runner.plan.schedule(times)
             self.wtab = torch.tensor(ws, dtype=torch.float32, device=img.device)
         self.replays = dict(guided=0, cond=0)
 
@@ -1062,8 +873,8 @@ class _EagerStep:
         self.row0, self.row_bytes = self.tab.data_ptr(), self.tab.shape[1] * self.tab.element_size()
         # scheduled guidance: per evaluation, whether it is guided (host) and its weight (device)
         self.flags = self.wtab = None
-        if runner.scheduled:
-            self.flags, ws = runner.schedule(times)
+        if runner.plan.scheduled:
+            self.flags, ws = runner.plan.schedule(times)
             self.wtab = torch.tensor(ws, dtype=torch.float32, device=img.device)
         self.replays = dict(guided=0, cond=0)
 
@@ -1081,11 +892,9 @@ class _EagerStep:
         """schedule row i from ``img``; ``eps``: a guided NCHW eps to use instead of evaluating the UNet at ``ts[i]``"""
         img, (B, Cc, hw) = self.img, self.dims
         # a guided NCHW eps is "NHWC with one channel" over B*C planes
-        e, mode, w, bb, cc = self.eps(i) if eps is None else (eps.contiguous(), 0, 0.0, B * Cc, 1)
-        opts = dict(z=self.upd.draw(noise, static=False), want_x0=want_x0) if self.upd.NOISE else {}
-        if self.runner.form == "data":                  # the update reads v: it also takes the UNet's time and the two tables
-            opts.update(t=self.ts[i], tables=self.runner.v)
-        self.upd.launch(_stream(), img, e, mode, w, bb, cc, hw, self.row0 + i * self.row_bytes, self.nxt, **opts)
+        read = self.eps(i) if eps is None else _Read.guided(eps.contiguous(), B * Cc, 1)
+        z = self.upd.draw(noise, static=False) if self.upd.NOISE else None
+        self.upd.launch(_stream(), img, read, hw, self.row0 + i * self.row_bytes, self.nxt, z, want_x0, self.ts[i], self.runner.v)
         self.img, self.nxt = self.nxt, img
 
     def back(self):
@@ -1096,14 +905,11 @@ class _EagerStep:
         return self.img
 
 
-def _sampler_step(runner, sk, img, upd, times, tab, capture=True):
-    """the step object a sampler's loop walks its schedule with.  Captured in the common case: fused CFG evaluation on the
-    drop-in UNet and nothing asked of the update that only the eager step runs (noise dropout, dynamic thresholding -- an
-    update that does not honour them never sees them); ``hip_graph=False`` in the sampling kwargs (or SGDM_HIP_GRAPH=0) and
-    ``capture=False`` (PLMS: the eps is the caller's) turn the capture off"""
-    assert isinstance(upd, _VUpdate) == (runner.form == "data"), (upd.kind, runner.form)
-    on = capture and sk.get("hip_graph", True) and os.environ.get("SGDM_HIP_GRAPH", "1") != "0"
-    if on and runner.fused_cfg() and upd.noise_dropout == 0 and upd.dtp >= 1.0:
+def _sampler_step(runner, img, upd, times, tab, capture=True):
+    """the step object a sampler's loop walks its schedule with: the captured one where the plan says so
+    (SamplingPlan.captured), else the eager one"""
+    assert isinstance(upd, _VUpdate) == (runner.plan.form == "data"), (upd.kind, runner.plan.form)
+    if runner.plan.captured(upd, capture):
         return _GraphedStep.get(runner, img, upd, times, tab)
     return _EagerStep(runner, img, upd, times, tab)
 
@@ -1291,32 +1097,33 @@ class Schedule_DDPM(nn.Module):
         if h.parameterization not in ("eps", "x0", "v"):
             raise NotImplementedError()                                        # ddpm_sampler.py:162-163
         dev = self.betas.device
-        if sk.get("parameterization", h.parameterization) == "v" and "sqrt_alphas_cumprod" not in sk:
-            # a direct call: this object is the training schedule, so its own hparam and buffers stand in for the kwargs
-            sk = dict(sk, parameterization="v", sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
+        dkw = denoise_sample_fn_kwargs or {}
+        lv = self.learn_sigma
+        # a direct call (no schedule tables in the kwargs): this object is the training schedule, so its own hparam and
+        # buffers stand in for them
+        direct = "sqrt_alphas_cumprod" not in sk
+        plan = resolve_plan(sk, "native", _model_behind(denoise_sample_fn), dkw, T=timesteps, lv=lv,
+                            par="v" if direct and h.parameterization == "v" else None)
+        if direct and plan.par == "v":
+            sk = dict(sk, sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
                       sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps (rows of the chain)
         # sampling kwarg native_steps = K (not in the reference): a strided chain over K of the table's times
-        K = native_steps_option(sk, "native", timesteps)
+        K = plan.native_steps
         times = np.arange(timesteps, dtype=np.int64) if K is None else native_times(K, timesteps)
-        lv = self.learn_sigma
-        if lv:
-            lv_native_option(sk)
-            sk = dict(sk, lv_native=True)                # the step runner hands the update the raw 2C-wide output
         # the 'x0' rows (0, -1) never read the infinite entries of a zero-terminal-SNR table, and the 'v' rows of the
         # learned-variance update never divide by sqrt(alphas_cumprod): nothing to refuse there
-        visited = None if h.parameterization == "x0" or (lv and h.parameterization == "v") else \
-            self.alphas_cumprod.detach().cpu().numpy()[times[list(range(len(times))) if order is None else [int(i) for i in order]]]
-        form = v_form_option(sk, "native", visited)
+        if not (h.parameterization == "x0" or (lv and h.parameterization == "v")):
+            plan.visits(self.alphas_cumprod.detach().cpu().numpy()[
+                times[list(range(len(times))) if order is None else [int(i) for i in order]]])
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         if type(temperature) == float or isinstance(temperature, int):
             temperature = [float(temperature)] * timesteps
         total = len(times)
         snaps = _Snapshots(total, sk)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        clip = 1 if sk["clip_denoised"] else 0
-        kind = "lv_native" if lv else "v_native" if form == "data" else "ddpm"
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev, plan=plan)
+        kind = "lv_native" if lv else "v_native" if plan.form == "data" else "ddpm"
         tab = None
         if K is not None or lv:
             # the chain's own coefficients, float64 from the fp32 alphas_cumprod of the visited times (per-step temperatures:
@@ -1324,13 +1131,12 @@ class Schedule_DDPM(nn.Module):
             tab, _ = native_rows(self.alphas_cumprod.detach().cpu().double().numpy()[times], kind, h.parameterization,
                                  [temperature[int(s)] for s in times])
         if lv:
-            upd = _LVUpdate(kind, sk, clip)
-        elif form == "data":
-            upd, tab = _VUpdate(kind, sk, clip, noise=True), (self.vstep_table(temperature) if tab is None else tab)
+            upd = _LVUpdate(kind, plan)
+        elif plan.form == "data":
+            upd, tab = _VUpdate(kind, plan, noise=True), (self.vstep_table(temperature) if tab is None else tab)
         else:
-            upd, tab = _DDUpdate(kind, sk, clip), (self.step_table(temperature) if tab is None else tab)
-        upd.native_steps = K
-        stepper = _sampler_step(runner, sk, img, upd, times, tab)
+            upd, tab = _DDUpdate(kind, plan), (self.step_table(temperature) if tab is None else tab)
+        stepper = _sampler_step(runner, img, upd, times, tab)
         for i in (reversed(range(0, total)) if order is None else order):
             want = i in snaps.rows
             stepper.step(i, None if noise_fn is None else noise_fn(i).to(dev), want)
@@ -1381,33 +1187,38 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def sample(self, shape, sampling_kwargs=None, **kwargs):
-        native_steps_option(sampling_kwargs, self.sampler_type, self.ddpm_num_timesteps)
+        if self.sampler_type not in ("ddim", "plms"):
+            raise NotImplementedError
         self.make_schedule(sampling_kwargs=sampling_kwargs)
         # step_indices (teacher-forced tests) visits only those table rows
         rows = kwargs.get("step_indices") if self.sampler_type == "ddim" else None
         times = self.ddim_timesteps if rows is None else self.ddim_timesteps[[int(i) for i in rows]]
-        v_form_option(sampling_kwargs, self.sampler_type, sampling_kwargs["alphas_cumprod"].detach().float().cpu().numpy()[times])
-        if self.sampler_type == "ddim":
-            return self.ddim_sampling(shape, sampling_kwargs=sampling_kwargs, **kwargs)
-        if self.sampler_type == "plms":
-            return self.plms_sampling(shape, sampling_kwargs=sampling_kwargs, **kwargs)
-        raise NotImplementedError
+        visited = sampling_kwargs["alphas_cumprod"].detach().float().cpu().numpy()[times]
+        loop = self.ddim_sampling if self.sampler_type == "ddim" else self.plms_sampling
+        return loop(shape, sampling_kwargs=sampling_kwargs, ac_visited=visited, **kwargs)
+
+    def _plan(self, sk, denoise_sample_fn, dkw, ac_visited):
+        return resolve_plan(sk, self.sampler_type, _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps,
+                            ac_visited=ac_visited)
 
     @torch.no_grad()
-    def plms_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, **kwargs):
+    def plms_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, ac_visited=None,
+                      **kwargs):
         """ddim_plms_sampler.py:394-482: pseudo linear multistep.  Per step ONE UNet evaluation at 2B (two on the
         first step), the guided eps kept as a [B,3,H,W] tensor for the Adams-Bashforth history, and the eager DDIM step
         given that eps (p_sample_plms == p_sample_ddim with a given eps, ddim_plms_sampler.py:484-525); no captured step.
         RNG order of the reference: x_T, then one randn per p_sample_plms call (num_steps + 1 draws)."""
         sk = sampling_kwargs
         dev = torch.device(self.device)
+        dkw = denoise_sample_fn_kwargs or {}
+        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        upd = _DDUpdate("ddim", sk, 1 if sk["clip_denoised"] else 0, sk["temperature"])
-        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, self.step_table, capture=False)
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev, plan=plan)
+        upd = _DDUpdate("ddim", plan, sk["temperature"])
+        stepper = _sampler_step(runner, img, upd, self.ddim_timesteps, self.step_table, capture=False)
         B, Cc, hw = stepper.dims
         draws = iter(range(total + 1))
 
@@ -1445,11 +1256,13 @@ class DDIMSampler(object):
         return snaps.result(stepper, shape)
 
     @torch.no_grad()
-    def ddim_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, **kwargs):
+    def ddim_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, ac_visited=None,
+                      **kwargs):
         sk = sampling_kwargs
         dev = torch.device(self.device)
-        img = _start_image(shape, kwargs.get("x_T"), dev)
         dkw = dict(denoise_sample_fn_kwargs or {})
+        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)
+        img = _start_image(shape, kwargs.get("x_T"), dev)
         vis = sk.get("vis")
         vis_noise = kwargs.get("vis_noise")                     # tests: the start noise a `vis` branch would draw
 
@@ -1481,6 +1294,7 @@ class DDIMSampler(object):
             dkw["layout"] = dkw["layout"][:ns].repeat_interleave(nw, 0)
             assert len(cs) == len(img) == len(dkw["layout"])
             dkw["cond_scale"] = cs
+            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)          # a tensor weight: no longer the fused step
         if should_vis("chainvis"):
             # conditional / unconditional chain pairs from the same start noise (ddim_plms_sampler.py:157-175)
             ns = vis.chainvis_c.samples
@@ -1488,17 +1302,17 @@ class DDIMSampler(object):
             dkw["cond"] = dkw["cond"][:ns].repeat_interleave(2, 0)
             assert len(dkw["cond"]) == len(img)
             dkw["p0"] = torch.tensor([1, 0], device=dev, dtype=torch.float32).repeat(ns)
+            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)          # p0: likewise
         shape = tuple(img.shape)
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
         snaps = _Snapshots(total, sk, host=True)
-        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev)
-        clip = 1 if sk["clip_denoised"] else 0
-        if runner.form == "data":
-            upd, tab = _VUpdate("v_ddim", sk, clip, noise=True), self.vstep_table(sk["temperature"])
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev, plan=plan)
+        if plan.form == "data":
+            upd, tab = _VUpdate("v_ddim", plan, noise=True), self.vstep_table(sk["temperature"])
         else:
-            upd, tab = _DDUpdate("ddim", sk, clip, sk["temperature"]), self.step_table
-        stepper = _sampler_step(runner, sk, img, upd, self.ddim_timesteps, tab)
+            upd, tab = _DDUpdate("ddim", plan, sk["temperature"]), self.step_table
+        stepper = _sampler_step(runner, img, upd, self.ddim_timesteps, tab)
         # step_indices (teacher-forced tests): visit only these table indices, in the order given
         visit = kwargs.get("step_indices")
         for index in (reversed(range(total)) if visit is None else map(int, visit)):
@@ -1581,8 +1395,9 @@ class PNDM_Sampler(object):
     def sample(self, shape, sampling_kwargs, log_num_per_prog=100, denoise_sample_fn=None, denoise_sample_fn_kwargs=None,
                **kwargs):
         sk = sampling_kwargs
-        native_steps_option(sk, "pndm", self.ddpm_num_timesteps)
-        v_form_option(sk, "pndm")                   # (its own schedule: no zero alphas_cumprod of the model's to visit)
+        dkw = denoise_sample_fn_kwargs or {}
+        # (its own schedule: no zero alphas_cumprod of the model's to visit)
+        plan = resolve_plan(sk, "pndm", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps)
         n = sk["num_timesteps"]
         times, tab = self.plan(n)
         if n > 250:
@@ -1591,8 +1406,8 @@ class PNDM_Sampler(object):
         dev = torch.device(self.device)
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
-        stepper = _sampler_step(runner, sk, img, _PNDMUpdate("pndm", sk, 0), times, tab)
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev, plan=plan)
+        stepper = _sampler_step(runner, img, _PNDMUpdate("pndm", plan), times, tab)
         for k in range(len(times)):
             stepper.step(k)
         img = stepper.final()
@@ -1688,19 +1503,18 @@ class DPMSolverSampler(object):
         sk = sampling_kwargs
         if sk.get("dtp", 1) < 1.0:
             raise ValueError("dpmsolver: dynamic thresholding (dtp < 1) is not implemented for this sampler")
-        native_steps_option(sk, "dpmsolver", self.ddpm_num_timesteps)
-        form = v_form_option(sk, "dpmsolver")
-        ts, tab = self.plan(sk, form)
-        v_form_option(sk, "dpmsolver", sk["alphas_cumprod"].detach().float().cpu().numpy()[ts])
+        dkw = denoise_sample_fn_kwargs or {}
+        plan = resolve_plan(sk, "dpmsolver", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps)
+        ts, tab = self.plan(sk, plan.form)          # (the table, and its times with it, is built for the form)
+        plan.visits(sk["alphas_cumprod"].detach().float().cpu().numpy()[ts])
         dev = torch.device(self.device)
         # a private copy: the trajectory is updated in place in the captured step
         img = _start_image(shape, kwargs.get("x_T"), dev, copy=True)
-        runner = _StepRunner(denoise_sample_fn, denoise_sample_fn_kwargs or {}, sk, dev)
+        runner = _StepRunner(denoise_sample_fn, dkw, sk, dev, plan=plan)
         total = len(ts)
         snaps = _Snapshots(total, sk)
-        clip = 1 if sk["clip_denoised"] else 0
-        upd = _VUpdate("v_dpmsolver", sk, clip, noise=False) if form == "data" else _DPMUpdate("dpmsolver", sk, clip)
-        stepper = _sampler_step(runner, sk, img, upd, ts, tab)
+        upd = _VUpdate("v_dpmsolver", plan, noise=False) if plan.form == "data" else _DPMUpdate("dpmsolver", plan)
+        stepper = _sampler_step(runner, img, upd, ts, tab)
         for index in reversed(range(total)):
             stepper.step(index)
             if index in snaps.rows:
@@ -1837,7 +1651,6 @@ class LatentDiffusion(nn.Module):
         if self.progressive is not None and sampling_method in ("ddim", "dpmsolver"):
             for k, v in dict(num_timesteps=self.progressive, ddim_eta=0, timestep_spacing="trailing", cfg_distilled=True).items():
                 sk.setdefault(k, v)
-        native_steps_option(sk, sampling_method, self.hparams.num_timesteps)     # refused on every other sampler
         kwargs.pop("condition_kwargs", None)
         samples, inter = self.sampler_list[sampling_method].sample(
             shape=shape, denoise_sample_fn=self.denoise_sample_fn, sampling_kwargs=sk, **kwargs)
@@ -1845,7 +1658,7 @@ class LatentDiffusion(nn.Module):
         inter["pred_x0"] = to_uint8(inter["pred_x0"])
         # end of a trajectory: the one place this path synchronises anyway -- a conv launch whose balanced tail timed out has
         # poisoned its outputs with NaN and flagged its workspace; raise here instead of handing NaN images on
-        unet = _unet_of(getattr(self.denoise_sample_fn, "_sgdm_inner", self.denoise_sample_fn))
+        unet = _model_behind(self.denoise_sample_fn)
         if unet is not None:
             for eng in list(unet._engines.values()):
                 eng.check_health()

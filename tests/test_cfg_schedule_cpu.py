@@ -124,7 +124,7 @@ def test_native_sampler_and_the_non_fused_kinds_of_step_refuse(monkeypatch):
     with pytest.raises(ValueError, match="fused-CFG"):
         d.p_sample_loop("ddim", (1, 3, 4, 4), _sk(cfg_rescale=0.5), denoise_sample_fn_kwargs=dict(cond_scale=2.0),
                         x_T=torch.zeros(1, 3, 4, 4))
-    # the kinds of step _StepRunner.fused_cfg() says no to, on (a stand-in for) the drop-in UNet
+    # the kinds of step SamplingPlan.fused says no to, on (a stand-in for) the drop-in UNet
     from sgdm_amd.unet import UNetModelBase
 
     class Fake(UNetModelBase):
@@ -132,6 +132,7 @@ def test_native_sampler_and_the_non_fused_kinds_of_step_refuse(monkeypatch):
 
         def __init__(self):
             torch.nn.Module.__init__(self)
+            self.condition = dict(scale_type="imagen")      # (the plan of an accepted step states how its halves are read)
 
         def forward_with_cond_scale(self, *a, **k):
             raise AssertionError("evaluated")

@@ -389,7 +389,7 @@ def test_p_sample_loop_picks_the_form(zt, monkeypatch):
     class Stop(Exception):
         pass
 
-    def runner(fn, kwargs, sk=None, dev=None):
+    def runner(fn, kwargs, sk=None, dev=None, plan=None):
         seen.append((sk.get("v_form"), sk.get("timestep_spacing")))
         raise Stop
     monkeypatch.setattr(Dm, "_StepRunner", runner)

@@ -19,14 +19,16 @@ class AttrDict(dict):
     __getattr__ = dict.__getitem__
 
 
-def model_and_guidance(name):
+def model_and_guidance(name, **ctor):
+    """``ctor``: constructor arguments that differ from the golden entry's (the weights are then drawn for the model's own shapes)"""
     entry = INDEX[name]
-    kw = dict(entry["ctor"])
+    kw = dict(entry["ctor"], **ctor)
     cond = AttrDict(scale_type="imagen")
     if entry["layout_dim"]:
         cond[kw["condition_method"]] = AttrDict(layout_dim=entry["layout_dim"])
     m = (UNetModel if entry["kind"] == "unet_fast" else UNetModelCA)(condition=cond, **kw)
-    m.load_state_dict(weights_from_seed(entry["manifest"], entry["seed"]))
+    manifest = [(k, tuple(v.shape)) for k, v in m.state_dict().items()] if ctor else entry["manifest"]
+    m.load_state_dict(weights_from_seed(manifest, entry["seed"]))
     m = m.cuda().eval()
     m.hip_precision = "f16x3"
     batch = synth_batch(kw["condition_method"], B, S, kw["cond_dim"], entry["layout_dim"], seed=23)
@@ -39,15 +41,77 @@ def skw(steps, **kw):
                      temperature=1.0, noise_dropout=0, random_sample_condition=False, return_inter_dict=True), **kw)
 
 
+def digest(tag, img, inter):
+    for key, t in [("sample", img)] + sorted(inter.items()):
+        t = t.detach().cpu().contiguous()
+        print(f"{tag} {key} {tuple(t.shape)} {hashlib.sha256(t.numpy().tobytes()).hexdigest()}", flush=True)
+
+
 def run(tag, diff, method, sk, dkw, **extra):
     torch.manual_seed(1234)
     sk = dict(sk, sampling_method=method, alphas_cumprod=diff.sampler.alphas_cumprod)
     with torch.no_grad():
         img, inter = diff.sampler_list[method].sample(shape=(B, 3, S, S), sampling_kwargs=sk, denoise_sample_fn=diff.denoise_sample_fn,
                                                       denoise_sample_fn_kwargs=dict(dkw), **extra)
-    for key, t in [("sample", img)] + sorted(inter.items()):
-        t = t.detach().cpu().contiguous()
-        print(f"{tag} {key} {tuple(t.shape)} {hashlib.sha256(t.numpy().tobytes()).hexdigest()}", flush=True)
+    digest(tag, img, inter)
+
+
+def run_loop(tag, diff, method, sk, dkw, **extra):
+    """through ``p_sample_loop`` (what the hparams add to the kwargs: the data form on a zero-terminal-SNR schedule); uint8"""
+    torch.manual_seed(1234)
+    with torch.no_grad():
+        img, inter = diff.p_sample_loop(method, (B, 3, S, S), dict(sk, sampling_method=method), denoise_sample_fn_kwargs=dict(dkw),
+                                        **extra)
+    digest(tag, img, inter)
+
+
+SHORT = dict(step_indices=[999, 888, 777, 500, 111, 1, 0])      # 888, 777, 111 and 0 are snapshot steps
+
+
+def options(name, m, dkw, diff, vp, vk):
+    """the sampling options on one model: the guidance schedule, the data form of 'v' (also on a zero-terminal-SNR schedule),
+    a strided native chain, a distilled student's step and (unet_fast) perturbed-attention guidance; eager and captured"""
+    zt = LatentDiffusion(device="cuda", **dict(bench.MODEL_PARAMS, parameterization="v", zero_terminal_snr=True))
+    zt.set_denoise_fn(m.forward, m.forward_with_cond_scale)
+    for graph in (False, True):
+        g = "graph" if graph else "eager"
+        sched = dict(cfg_rescale=0.7, cfg_interval=(200, 800), hip_graph=graph)
+        run(f"{name} native-short rescale+interval {g}", diff, "native", skw(1000, **sched), dkw, **SHORT)
+        run(f"{name} ddim-10 rescale+interval {g}", diff, "ddim", skw(10, **sched), dkw)
+        run(f"{name} pndm-10 rescale+interval {g}", diff, "pndm", skw(10, **sched), dkw)
+        data = dict(vk, v_form="data", hip_graph=graph)
+        run(f"{name} native-short v_form=data {g}", vp, "native", skw(1000, **data), dkw, **SHORT)
+        run(f"{name} ddim-10 v_form=data {g}", vp, "ddim", skw(10, **data), dkw)
+        run(f"{name} dpmsolver-10 v_form=data {g}", vp, "dpmsolver", skw(10, **data), dkw)
+        run_loop(f"{name} native-short ztsnr {g}", zt, "native", skw(1000, hip_graph=graph), dkw, **SHORT)
+        run_loop(f"{name} ddim-10 ztsnr {g}", zt, "ddim", skw(10, hip_graph=graph), dkw)
+        run_loop(f"{name} dpmsolver-10 ztsnr {g}", zt, "dpmsolver", skw(10, hip_graph=graph), dkw)
+        run(f"{name} native_steps=10 {g}", diff, "native", skw(1000, native_steps=10, hip_graph=graph), dkw)
+        run(f"{name} ddim-10 cfg_distilled {g}", diff, "ddim", skw(10, cfg_distilled=True, hip_graph=graph), dkw)
+        run(f"{name} dpmsolver-10 cfg_distilled {g}", diff, "dpmsolver", skw(10, cfg_distilled=True, hip_graph=graph), dkw)
+        if not isinstance(m, UNetModel):
+            continue                                                    # PAG: the self-attention block only
+        run(f"{name} native-short pag {g}", diff, "native", skw(1000, pag_scale=1.5, hip_graph=graph), dkw, **SHORT)
+        for method in ("ddim", "pndm", "dpmsolver"):
+            run(f"{name} {method}-10 pag {g}", diff, method, skw(10, pag_scale=1.5, hip_graph=graph), dkw)
+        run(f"{name} ddim-10 pag all+drop_cond+interval {g}", diff, "ddim",
+            skw(10, pag_scale=1.5, pag_layers="all", pag_drop_cond=True, cfg_interval=(200, 800), hip_graph=graph), dkw)
+    if isinstance(m, UNetModel):
+        run(f"{name} plms-10 pag eager", diff, "plms", skw(10, pag_scale=1.5), dkw)
+
+
+def learned_variance():
+    """a 2C-wide unet_fast model: the learned-variance 'native' update, full chain and strided, and the narrow head of 'ddim'"""
+    name = "uf_label_c32_s16"
+    m, dkw = model_and_guidance(name, out_channels=6)
+    lv = LatentDiffusion(device="cuda", **dict(bench.MODEL_PARAMS, parameterization="eps", learn_sigma=True))
+    lv.set_denoise_fn(m.forward, m.forward_with_cond_scale)
+    for graph in (False, True):
+        g = "graph" if graph else "eager"
+        run(f"{name}/2C native-short learn_sigma {g}", lv, "native", skw(1000, hip_graph=graph), dkw, **SHORT)
+        run(f"{name}/2C native_steps=10 learn_sigma {g}", lv, "native", skw(1000, native_steps=10, hip_graph=graph), dkw)
+        run(f"{name}/2C ddim-10 narrow head {g}", lv, "ddim", skw(10, hip_graph=graph), dkw)
+    print(f"{name}/2C captured steps {len(m.__dict__.get('_hip_graph_steps', {}))}", flush=True)
 
 
 def main():
@@ -56,7 +120,7 @@ def main():
         m, dkw = model_and_guidance(name)
         diff = LatentDiffusion(device="cuda", **bench.MODEL_PARAMS)
         diff.set_denoise_fn(m.forward, m.forward_with_cond_scale)
-        short = dict(step_indices=[999, 888, 777, 500, 111, 1, 0])      # 888, 777, 111 and 0 are snapshot steps
+        short = SHORT
         for graph in (False, True):
             g = "graph" if graph else "eager"
             run(f"{name} native-short {g}", diff, "native", skw(1000, hip_graph=graph), dkw, **short)
@@ -93,6 +157,9 @@ def main():
         for method, sk, extra in (("native", skw(1000), short), ("ddim", skw(10), {}), ("plms", skw(10), {}),
                                   ("pndm", skw(10), {}), ("dpmsolver", skw(10), {}), ("ddim", skw(10, dtp=0.9), {})):
             run(f"{name} {method} plain-callable dtp={sk['dtp']}", plain, method, sk, dkw, **extra)
+        options(name, m, dkw, diff, vp, vk)
+        print(f"{name} captured steps {len(m.__dict__.get('_hip_graph_steps', {}))}", flush=True)
+    learned_variance()
 
 
 if __name__ == "__main__":
