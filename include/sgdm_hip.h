@@ -877,6 +877,50 @@ int sgd_adamw_ema_step(const sgd_opt_tensor* table, const int32_t* chunk_start, 
                        poisoned step never reaches parameters, moments or EMA shadows */, void* stream);
 
 /* --------------------------------------------------------------------------------------
+ * Global-norm gradient clipping on the optimizer's tensor table (additive in ABI 25; csrc/gradclip.hip, csrc/misc.hip).
+ * The three entries take the table and the chunk_start prefix of sgd_adamw_ema_step and read only g and n of a row
+ * (g == NULL: the row contributes nothing; p / m / v / ema may be NULL for sgd_grad_norm and sgd_grad_scale).  A g may sit on
+ * any 4-byte boundary.
+ *
+ * sgd_clip_record: DEVICE, 32 bytes, zero it once; it lives as long as the caller wants the counters to run.  norm, coef and
+ * skip describe the LAST sgd_grad_norm; the two counters run on.  Nothing here is read back by the host on the product path:
+ * the coefficient goes from the norm kernel to the step through device memory.
+ *
+ * sgd_grad_norm: norm = sqrt(sum g^2) over every row, in two launches.  Stage 1: one 256-thread block per chunk, each
+ *   thread sums its squares in DOUBLE (the square of an fp32 value is exact in double, so gradients whose squares leave fp32's
+ *   normal range in either direction count in full), xor-shuffles inside the wave, a fixed-order fold over the four waves, one
+ *   double per chunk into partials[0 .. total_chunks).  Stage 2: one block, thread i sums partials[i], [i + 256], ... in double,
+ *   the same fold, norm = (float)sqrt(sum): one rounding to fp32 at the end.  No atomics and no arrival counters: the result
+ *   depends on the list of n and on the gradient values, never on addresses, grid scheduling or timing -- replicas that hold
+ *   bit-identical gradients reach bit-identical coefficients.
+ *   max_norm finite and > 0: coef = min(1, max_norm / (norm + 1e-6f)), fp32, each operation rounded (the formula of
+ *   torch.nn.utils.clip_grad_norm_).  Any other max_norm (0, negative, inf, NaN): coef = 1 -- measure only.
+ *   norm not finite: skip = 1, coef = 0, nonfinite_steps += 1.  Otherwise skip = 0 and clipped_steps += 1 when coef < 1.
+ * sgd_grad_scale: g = g * rec->coef (one rounded fp32 product) in place; every block returns at once when rec->coef == 1 or
+ *   rec->skip, so an unclipped or a void step writes nothing.  (The route for optimizers that are not sgd_adamw_ema_clip_step.)
+ * sgd_adamw_ema_clip_step: sgd_adamw_ema_step with g replaced by the rounded product g * rec->coef as it is loaded -- the
+ *   gradients are not rewritten -- and void when *skip_if_nonzero != 0 OR rec->skip.  It is a second instantiation of the same
+ *   kernel body: with rec->coef == 1 it computes the bits of sgd_adamw_ema_step, otherwise the bits of sgd_adamw_ema_step on
+ *   gradients scaled by sgd_grad_scale.
+ * SGD_ERR_ARG, nothing launched: a NULL table, chunk_start, partials or rec; count or total_chunks <= 0. */
+typedef struct {
+    float   norm;            /* total L2 norm of this step's gradients, before clipping */
+    float   coef;            /* what the step multiplies g by: min(1, max_norm / (norm + 1e-6f)); 1 when not clipping */
+    int32_t skip;            /* this step: 1 iff norm is not finite */
+    int32_t clipped_steps;   /* running count of steps with coef < 1 */
+    int32_t nonfinite_steps; /* running count of steps with skip == 1 */
+    int32_t pad[3];
+} sgd_clip_record;
+int sgd_grad_norm(const sgd_opt_tensor* table, const int32_t* chunk_start, int32_t count, int32_t total_chunks,
+                  double* partials /* DEVICE [total_chunks], scratch */, float max_norm, sgd_clip_record* rec, void* stream);
+int sgd_grad_scale(const sgd_opt_tensor* table, const int32_t* chunk_start, int32_t count, int32_t total_chunks,
+                   const sgd_clip_record* rec, void* stream);
+int sgd_adamw_ema_clip_step(const sgd_opt_tensor* table, const int32_t* chunk_start, int32_t count, int32_t total_chunks,
+                            float lr, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                            float bias_correction1, float bias_correction2, float ema_one_minus_decay,
+                            const float* skip_if_nonzero, const sgd_clip_record* rec, void* stream);
+
+/* --------------------------------------------------------------------------------------
  * Gradient exchange (ABI 18; SURVEY 8(b), last row).  Replaces the per-bucket all-reduce torch DDP issues under
  * pl.trainer.strategy=ddp (config/pl/default.yaml:2, README.md:84-94) for hosts that do not go through torch.distributed:
  * bucket[0..count) = SUM over the ranks of `nccl_comm` (an ncclComm_t the caller created), in place, fp32, enqueued on

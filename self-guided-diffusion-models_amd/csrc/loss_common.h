@@ -5,8 +5,10 @@
 // live here once: the simple terms of the pairs agree bit for bit because they ARE the same code, which the tests assert
 // (tests/test_hip_learned_variance.py, tests/test_hip_distill.py, tests/test_hip_progressive.py).
 //
+// (gradclip.hip, the gradient norm of the optimizer's clip, takes loss_block_sum from here and nothing else.)
+//
 // Everything here is __device__ __forceinline__ (or host inline) and is therefore compiled under the flags of the file that
-// includes it.  All four includers are -ffp-contract=off (build.py: FILE_FLAGS): every product is rounded before it is added,
+// includes it.  All includers are -ffp-contract=off (build.py: FILE_FLAGS): every product is rounded before it is added,
 // so the gradient reproduces a torch-fp32 restatement bit for bit.  A file compiled with contraction on must not include this.
 #pragma once
 #include "sgdm_common.h"

@@ -505,14 +505,24 @@ extern "C" int sgd_cfg_combine(const float* eps_nhwc, int32_t cfg_mode, float w,
 namespace {
 constexpr int OPT_CHUNK = 4096;
 
+// CLIP: the step of sgd_adamw_ema_clip_step -- every gradient is multiplied by the coefficient sgd_grad_norm (csrc/gradclip.hip)
+// left in `rec` as it is loaded, and the step is void when that record says the norm was not finite.  One body for both
+// instantiations: everything behind the load of g is the same code.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_ema_kernel(const sgd_opt_tensor* __restrict__ table,
                                                         const int32_t* __restrict__ chunk_start, int count, float lr,
                                                         float omb1, float b2, float omb2, float eps, float wd,
-                                                        float bc1, float bc2, float omd, const float* __restrict__ skip) {
+                                                        float bc1, float bc2, float omd, const float* __restrict__ skip,
+                                                        const sgd_clip_record* __restrict__ rec) {
     // the step is void when the gradients are: a balanced-tail time-out of the backward program poisons its tiles with NaN
     // and raises the health flag the caller hands in (all-reduced over the ranks of a data-parallel job) -- parameters,
     // moments and EMA shadows stay as they are and the host raises at its next look at the flag (unet._Engine.poll_health)
     if (skip && *skip != 0.f) return;
+    float coef = 1.f;
+    if constexpr (CLIP) {
+        if (rec->skip) return;                  // a non-finite gradient norm voids the step in the same way
+        coef = rec->coef;
+    }
     // the tensor that owns this chunk: last t with chunk_start[t] <= blockIdx.x
     int lo = 0, hi = count - 1;
     const int b = blockIdx.x;
@@ -528,7 +538,13 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const sgd_opt_tensor* __
         if (e >= t.n) break;
         float p = t.p[e];
         if (t.g) {
-            const float g = t.g[e];
+            float g = t.g[e];
+            if constexpr (CLIP) {
+                // one rounded fp32 product, as if the gradient had been rewritten in place: this file is compiled with
+                // contraction on, and g * coef - m must not become one fma
+                g = __fmul_rn(g, coef);
+                SGD_ROUNDED(g);
+            }
             float m = t.m[e], v = t.v[e];
             p *= decay_f;
             m = m + omb1 * (g - m);
@@ -554,9 +570,24 @@ extern "C" int sgd_adamw_ema_step(const sgd_opt_tensor* table, const int32_t* ch
     SGD_CLEAR_ERR();
     if (!table || !chunk_start || count <= 0 || total_chunks <= 0 || bias_correction1 <= 0.f || bias_correction2 <= 0.f)
         return SGD_ERR_ARG;
-    hipLaunchKernelGGL(adamw_ema_kernel, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_start,
+    hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_start,
                        count, lr, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2,
-                       ema_one_minus_decay, skip_if_nonzero);
+                       ema_one_minus_decay, skip_if_nonzero, (const sgd_clip_record*)nullptr);
+    return sgd_check_launch();
+}
+
+extern "C" int sgd_adamw_ema_clip_step(const sgd_opt_tensor* table, const int32_t* chunk_start, int32_t count,
+                                       int32_t total_chunks, float lr, float one_minus_beta1, float beta2,
+                                       float one_minus_beta2, float eps, float weight_decay, float bias_correction1,
+                                       float bias_correction2, float ema_one_minus_decay, const float* skip_if_nonzero,
+                                       const sgd_clip_record* rec, void* stream) {
+    SGD_CLEAR_ERR();
+    if (!table || !chunk_start || !rec || count <= 0 || total_chunks <= 0 || bias_correction1 <= 0.f ||
+        bias_correction2 <= 0.f)
+        return SGD_ERR_ARG;
+    hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_start,
+                       count, lr, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2,
+                       ema_one_minus_decay, skip_if_nonzero, rec);
     return sgd_check_launch();
 }
 

@@ -146,6 +146,10 @@ SIGNATURES = {
     "sgd_q_sample": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, vp]),
     "sgd_mse_loss": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "sgd_adamw_ema_step": (i32, [vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp, vp]),
+    # global-norm clipping on the optimizer's table (table, chunk_start, partials and the sgd_clip_record are DEVICE memory)
+    "sgd_grad_norm": (i32, [dvp, dvp, i32, i32, dvp, f32, dvp, vp]),
+    "sgd_grad_scale": (i32, [dvp, dvp, i32, i32, dvp, vp]),
+    "sgd_adamw_ema_clip_step": (i32, [vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp, dvp, vp]),
     "sgd_exchange_bind": (i32, [C.c_char_p]),
     "sgd_allreduce_bucket": (i32, [vp, vp, i64, vp]),
     "sgd_timestep_embedding": (i32, [vp, vp, i32, i32, i32, vp, vp]),
