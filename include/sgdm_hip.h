@@ -332,6 +332,39 @@ int sgd_attention_split(const float* q, int32_t q_ld, int32_t q_hs,
 int sgd_attention_identity(const float* v, int32_t kv_ld, int32_t kv_hs,
                            int32_t batch, int32_t heads, int32_t t, int32_t d,
                            float* out, int32_t out_ld, void* stream);
+/* Self-attention guidance (Hong et al. 2023; sampling kwarg sag_scale, sgdm_amd/diffusion.py; no counterpart in the reference),
+ * csrc/sag.hip.  sgd_attention_colmass: the attention each key RECEIVES, averaged over the heads -- the column sums of the
+ * softmax map the cores above never materialise, re-formed from q, k and the lse they wrote:
+ *   mass[b, j] = (1 / heads) sum_h sum_i exp(scale * <q[b,i,h,:], k[b,j,h,:]> - lse[b,h,i])         (sum_j mass[b, j] = tq)
+ * The addressing contract of the cores: d in {16, 32, 64, 128}, 16-byte loads, q and k 16-byte aligned, q_ld, q_hs, kv_ld, kv_hs
+ * multiples of 4 floats (padded head widths and both qkv orders are strides); any tq, tk >= 1 -- anything else is SGD_ERR_ARG,
+ * nothing launched.  Exact fp32 in every engine precision.  One workgroup owns 64 keys of one sample, a lane one key, and loops
+ * over heads and queries; the sums fold in a fixed order (the lane's own queries, then the workgroup's waves through LDS) without
+ * atomics: results are identical from run to run and between a captured and an eager launch.  Additive entry (ABI unchanged at
+ * 25). */
+int sgd_attention_colmass(const float* q, int32_t q_ld, int32_t q_hs, const float* k, int32_t kv_ld, int32_t kv_hs,
+                          const float* lse /* [batch, heads, tq] */, int32_t batch, int32_t heads, int32_t tq, int32_t tk,
+                          int32_t d, float scale, float* mass /* [batch, tk] */, void* stream);
+/* sgd_sag_degrade: the input of a SAG step's second evaluation in one launch.  Per sample n with a = sa_tab[t[n]],
+ * s = s1_tab[t[n]] (the training schedule at the UNet's time), o the first evaluation's output, each product rounded before it
+ * is added:
+ *   par 0 (eps): e = o, x0 = (x - s * e) / a;   par 1 (x0): x0 = o, e = (x - a * x0) / s;   par 2 (v): x0 = a * x - s * o,
+ *                                                                                                       e = a * o + s * x
+ *   hp[y, x] = sum_{k=-4..4} taps[k + 4] * x0[y, r_w(x + k)];   bl[y, x] = sum_k taps[k + 4] * hp[r_h(y + k), x]
+ *              (ascending k; r_n(i) = -i for i < 0, 2 (n - 1) - i for i >= n: torch's 'reflect')
+ *   M[y, x]  = mass[n, ((y * mh) / h) * mw + (x * mw) / w] > thr             (nearest upsampling, integer arithmetic)
+ *   x_deg    = a * (M ? bl : x0) + s * e
+ * x, x_deg are NCHW [b, c, h, w]; out_nhwc is [b, h*w, out_ld] and its channels [0, c) are read; out_copy, when not NULL,
+ * receives those rows densely ([b, h*w, c]: the first half of the pair the step kernels then read); taps_dev is a DEVICE
+ * float[9]; t a DEVICE int64 [b]: no by-value argument depends on the step, so one captured step replays for a trajectory.
+ * x0 / e are formed once per staged element and both blur passes run out of LDS (64x64 tiles with a 4-pixel halo).
+ * SGD_ERR_ARG, nothing launched: a NULL pointer (out_copy excepted), b or c <= 0, par out of range, out_ld < c, h or w < 5 (the
+ * reflection pad must be smaller than the side), mh / mw outside [1, h] / [1, w], x_deg == x.  Additive entry (ABI unchanged
+ * at 25). */
+int sgd_sag_degrade(const float* x, const float* out_nhwc, int32_t out_ld, int32_t par, const int64_t* t, const float* sa_tab,
+                    const float* s1_tab, const float* mass, int32_t mh, int32_t mw, float thr, const float* taps_dev /* DEVICE [9] */,
+                    int32_t b, int32_t c, int32_t h, int32_t w, float* x_deg, float* out_copy /* [b, h*w, c] or NULL */,
+                    void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Small glue kernels on the UNet boundary.

@@ -54,6 +54,9 @@ FILE_FLAGS["progressive.hip"] = ["-ffp-contract=off"]
 # gradclip.hip: the same -- the clip coefficient (sgd_grad_norm) is torch's fp32 formula operation by operation and
 # sgd_grad_scale's g * coef one rounded product; it includes loss_common.h for the block sum only
 FILE_FLAGS["gradclip.hip"] = ["-ffp-contract=off"]
+# sag.hip: the same -- the x0 / eps change of variables, the blur taps and the re-noise of self-attention guidance
+# (sgd_sag_degrade) are bit-equal to their torch-fp32 restatement only product by product
+FILE_FLAGS["sag.hip"] = ["-ffp-contract=off"]
 # pag.hip (sgd_attention_identity: a gather, no arithmetic) takes the global flags like every file not named here; _sources()
 # picks it up with the rest of csrc/
 # (loss.hip, lvloss.hip, distill.hip and progressive.hip share csrc/loss_common.h, which is compiled under the includer's flags:

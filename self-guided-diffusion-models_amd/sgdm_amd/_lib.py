@@ -113,6 +113,8 @@ SIGNATURES = {
     "sgd_attention": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp]),
     "sgd_attention_split": (i32, [vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp]),
     "sgd_attention_identity": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "sgd_attention_colmass": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "sgd_sag_degrade": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, f32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "sgd_attention_masked": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp]),
     "sgd_linear_attention": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]),
     "sgd_attention_bwd": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32,

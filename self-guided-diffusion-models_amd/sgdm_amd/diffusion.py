@@ -42,6 +42,11 @@ Also without a counterpart, perturbed-attention guidance (Ahn et al. 2024): the 
 ``pag_drop_cond`` (``pag_options``) make the second half of the doubled evaluation the same network with the self-attention map of
 the chosen layers replaced by the identity (unet.py: ``_engine(pag=...)``, include/sgdm_hip.h: sgd_attention_identity); the step
 kernels read the halves in their cfg form with w = s, in all five samplers; ``cond_scale`` is not read.
+Also without a counterpart, self-attention guidance (Hong et al. 2023): the sampling kwargs ``sag_scale`` = s, ``sag_layer``,
+``sag_threshold`` and ``sag_blur_sigma`` (``sag_options``) make a guided step TWO dependent evaluations at B -- the conditional one,
+then the same engine on the image whose x0 prediction is blurred where the chosen layer's attention mass exceeds the threshold
+(``_StepRunner.sag_degrade``; include/sgdm_hip.h: sgd_attention_colmass, sgd_sag_degrade) -- whose pair the step kernels read in
+their cfg form with w = s; one captured graph, no parallel branches.
 
 Per sampling step the host issues: one UNet evaluation at 2B (cond | uncond halves, doubled inside
 the boundary kernels) and ONE fused kernel doing CFG combine + x0 prediction + clip + posterior /
@@ -49,6 +54,8 @@ DDIM update + noise (include/sgdm_hip.h: sgd_ddpm_step / sgd_ddim_step).  RNG dr
 per-step mask uniform_ and z) are kept in the reference's order so seeded runs line up.
 """
 import copy
+import ctypes
+import math
 import os
 import warnings
 from functools import partial
@@ -61,7 +68,7 @@ from torch import nn
 from . import _lib as L
 from .sampling_plan import (LV_NATIVE_REFUSED, V_FORM_SAMPLERS, SamplingPlan, cfg_distilled_option, cfg_options,  # noqa: F401
                             cfg_schedule, lv_native_option, native_steps_option, pag_options, pag_scale_option, resolve_plan,
-                            v_form_option)
+                            sag_options, sag_scale_option, v_form_option)
 from .unet import UNetModelBase, _cfg_eval, _ptr
 
 
@@ -321,10 +328,10 @@ class _Read(NamedTuple):
         return cls(buf, 0, 0.0, b, c)
 
 
-def _v_tables(sk, dev, par=None):
+def _v_tables(sk, dev, par=None, always=False):
     """(sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod) as fp32 device tables when the parameterization (``par``: the
     plan's; None: as the sampling kwargs say) is 'v', else None ('eps', the default of a direct sampler call, and 'x0' convert
-    nothing).
+    nothing; ``always``: the tables whatever the parameterization -- self-attention guidance forms x0 and eps from them).
     ``p_sample_loop`` hands over the training schedule's buffers; a direct caller that passes only ``alphas_cumprod`` gets
     the square roots formed from it in double and rounded once (the fp32 ``alphas_cumprod`` resolves 1 - ac to ~6e-4 at
     t = 0, where the schedule's own table was rounded from float64: pass the tables where that matters)"""
@@ -332,7 +339,8 @@ def _v_tables(sk, dev, par=None):
     if par != "v":
         if par not in ("eps", "x0"):
             raise NotImplementedError(f"parameterization '{par}'")
-        return None
+        if not always:
+            return None
     sa, s1 = sk.get("sqrt_alphas_cumprod"), sk.get("sqrt_one_minus_alphas_cumprod")
     if sa is None or s1 is None:
         ac = sk["alphas_cumprod"].detach().double()
@@ -407,6 +415,13 @@ class _StepRunner:
         self.lib = L.load()
         self._drop = {}
         self.v = None if self.plan.lv else _v_tables(sk, dev, self.plan.par)
+        # self-attention guidance: the two schedule tables whatever the parameterization (``tables``: what a captured step
+        # keeps static copies of) and the blur's taps, float64 on the host and rounded once
+        self.tables, self.sag_taps = self.v, None
+        if self.plan.sag:
+            from .sag import gaussian_taps
+            self.tables = self.v or _v_tables(sk, dev, self.plan.par, always=True)
+            self.sag_taps = gaussian_taps(self.plan.sag[3]).float().to(dev)
 
     form = property(lambda self: self.plan.form)
 
@@ -455,6 +470,48 @@ class _StepRunner:
         L.check(self.lib.sgd_cfg_guide(_ptr(out), mode, _ptr(w_dev), self.plan.rescale, B, Cc, hw, _ptr(g), st), "sgd_cfg_guide")
         return g
 
+    def sag_record(self, eng):
+        """the tape record of the plan's ``sag_layer`` in ``eng``: its qkv / lse buffers outlive the evaluation (engine buffers
+        are never recycled)"""
+        layer = self.plan.sag[1]
+        return next(r for r in eng.tape if r["kind"] == "attn" and r["p"] == layer)
+
+    def sag_degrade(self, eng, x, t, pair, x_deg, mass, st, tables=None, taps=None):
+        """self-attention guidance between its two evaluations, after ``eng`` (batch B) has run on (x, t): the attention mass
+        of the plan's layer into ``mass`` [B, T] (sgd_attention_colmass), then the degraded image into ``x_deg`` and the
+        engine's output rows into the first half of ``pair`` [2B, hw, C] (sgd_sag_degrade).  ``tables`` / ``taps``: a captured
+        step's static copies"""
+        from .sag import PAR_ID
+        rec = self.sag_record(eng)
+        qkv, heads, dp = rec["qkv"], rec["heads"], rec["dp"]
+        hs, ko, _ = rec["qkv_layout"]
+        B, Cc, H, W = x.shape
+        ld = 3 * heads * dp
+        L.check(self.lib.sgd_attention_colmass(_ptr(qkv), ld, hs, ctypes.c_void_p(qkv.data_ptr() + 4 * ko), ld, hs,
+                                               _ptr(rec["lse"]), B, heads, rec["T"], rec["T"], dp, 1.0 / math.sqrt(rec["d"]),
+                                               _ptr(mass), st), "sgd_attention_colmass")
+        sa, s1 = tables or self.tables
+        mh, mw = rec["hw"]
+        L.check(self.lib.sgd_sag_degrade(_ptr(x), _ptr(eng.eps_nhwc), Cc, PAR_ID[self.plan.par], _ptr(t), _ptr(sa), _ptr(s1),
+                                         _ptr(mass), mh, mw, self.plan.sag[2], _ptr(self.sag_taps if taps is None else taps),
+                                         B, Cc, H, W, _ptr(x_deg), _ptr(pair), st), "sgd_sag_degrade")
+
+    def sag_pair(self, x, t):
+        """the guided evaluation of self-attention guidance, eager: [o ; o~] as [2B, hw, C].  Both evaluations are the
+        conditional one at B on ONE engine and draw like the model's single ``forward(cond_drop_prob=p0)``"""
+        B, Cc = x.shape[0], x.shape[1]
+        m, kw = self.model, self.kwargs
+        draw = (lambda: m._draw_mask(B, 0.0, x.device)) if self.cond_only_mask() else (lambda: None)
+        eng = m._run(x, t, kw.get("cond"), kw.get("layout"), draw(), B, self.head(Cc))
+        assert eng.eps_nhwc.shape[-1] == Cc, (tuple(eng.eps_nhwc.shape), Cc)
+        pair = torch.empty((2 * B, x[0, 0].numel(), Cc), device=x.device)
+        x_deg = torch.empty_like(x)
+        mass = torch.empty((B, self.sag_record(eng)["T"]), device=x.device)
+        self.sag_degrade(eng, x.contiguous(), t.contiguous(), pair, x_deg, mass, _stream())
+        assert m._run(x_deg, t, kw.get("cond"), kw.get("layout"), draw(), B, self.head(Cc)) is eng
+        pair[B:].copy_(eng.eps_nhwc.reshape(B, -1, Cc))
+        return pair
+
     def eps(self, x, t, guided=True, w_dev=None):
         """the evaluation at (x, t) as the ``_Read`` of the step kernel.  A scheduled trajectory's step object says whether
         this evaluation is ``guided`` and hands over its weight as a device float"""
@@ -467,10 +524,13 @@ class _StepRunner:
                 mask = m._draw_mask(B, 0.0, x.device) if self.cond_only_mask() else None
                 read = _Read.guided(m._run(x, t, kw.get("cond"), kw.get("layout"), mask, B, self.head(Cc)).eps_nhwc, B, Cc)
             else:
-                has_mask, p = self.drop_mask(B, x.device)
-                mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
-                eng = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc), plan.layers)
-                read = _Read(eng.eps_nhwc, plan.mode, plan.weight, B, Cc)
+                if plan.sag:
+                    out = self.sag_pair(x, t)
+                else:
+                    has_mask, p = self.drop_mask(B, x.device)
+                    mask = m._draw_mask(2 * B, p, x.device) if has_mask else None
+                    out = m._run(x, t, kw.get("cond"), kw.get("layout"), mask, 2 * B, self.head(Cc), plan.layers).eps_nhwc
+                read = _Read(out, plan.mode, plan.weight, B, Cc)
                 if plan.scheduled:
                     g = torch.empty((B, x[0, 0].numel(), Cc), device=x.device)
                     read = _Read.guided(self.guide(read.buf, read.mode, w_dev, B, Cc, x[0, 0].numel(), g, _stream()), B, Cc)
@@ -707,11 +767,12 @@ class _GraphedStep:
         prec = L.PREC_BY_NAME[m.hip_precision]
         # the engine of the doubled evaluation: with the C-row head where a learned-variance model's update ignores the
         # variance half, of the plan's PAG layer set; a distilled student's is the engine at B, its only one (the 2B engine
-        # and its workspace are never built)
+        # and its workspace are never built), and so is the one both evaluations of self-attention guidance run on
         head = runner.head(img.shape[1])
-        eng = m._engine((1 if plan.distilled else 2) * img.shape[0], img.shape[2], img.shape[3], prec, head, plan.layers)
+        eng =m._engine((1 if plan.distilled or plan.sag else 2) * img.shape[0], img.shape[2], img.shape[3], prec, head,
+                        plan.layers)
         # what only this place knows, then what the plan and the update say the capture bakes in of them
-        key = (id(eng), tuple(img.shape), sig(cond), sig(layout), None if runner.v is None else runner.v[0].numel(), head,
+        key = (id(eng), tuple(img.shape), sig(cond), sig(layout), None if runner.tables is None else runner.tables[0].numel(), head,
                plan.capture_key(), upd.capture_key())
         cache = m.__dict__.setdefault("_hip_graph_steps", {})
         g = cache.get(key)                                  # a hit keeps the cached step's update object (and its buffers):
@@ -724,7 +785,7 @@ class _GraphedStep:
                 del cache[k]                                # oldest first (dicts keep insertion order): a sweep over
                                                             # guidance weights / temperatures must not grow without bound
             g = cache[key] = cls(runner, eng, img, upd)
-        g.begin(img, cond, layout, times, tab, runner.v, runner)
+        g.begin(img, cond, layout, times, tab, runner.tables, runner)
         return g
 
     def __init__(self, runner, eng, img, upd):
@@ -746,14 +807,33 @@ class _GraphedStep:
         plan = runner.plan
         self.distilled = plan.distilled                 # ``eng`` is the engine at B and ``graph1`` the only graph
         img = self.img
-        if not self.distilled:
+        self.sag = plan.sag
+        if self.sag:
+            # self-attention guidance: ``eng`` is the engine at B and runs twice per replay, on ``img`` and on the degraded
+            # image -- one prepared input set each, named at the launch; both masks stay all-false (``us`` is only drawn
+            # into, twice per step, to consume the RNG like the model's own single evaluation does)
+            self.has_mask = runner.cond_only_mask()
+            self.us = torch.zeros(B, device=dev) if self.has_mask else None
+            self.mask = torch.zeros(B, dtype=torch.bool, device=dev) if self.has_mask else None
+            self.x_deg = torch.zeros_like(img)
+            self.pair = torch.zeros((2 * B, hw, Cc), device=dev)
+            self.mass = torch.zeros((B, runner.sag_record(eng)["T"]), device=dev)
+            self.taps = runner.sag_taps.clone()         # (sigma is part of the key: never refreshed)
+            self._inputs = eng.prepare(self.img, self.t, self.cond, self.layout, self.mask)
+            self._inputs_deg = eng.prepare(self.x_deg, self.t, self.cond, self.layout, self.mask)
+        elif not self.distilled:
             self.has_mask, self.p = runner.drop_mask(B, dev)
             self.u = torch.zeros(2 * B, device=dev)
             self.mask = torch.zeros(2 * B, dtype=torch.bool, device=dev)
             eng.prepare(self.img, self.t, self.cond, self.layout, self.mask if self.has_mask else None)
             self._inputs = eng._keep_inputs             # the captured launches read these buffers on every replay
-        # parameterization 'v': static copies of the two schedule tables (refreshed by begin()) and the converted eps
-        self.v = None if runner.v is None else tuple(torch.empty_like(a) for a in runner.v)
+        # parameterization 'v' / self-attention guidance: static copies of the two schedule tables (refreshed by begin());
+        # 'v': the converted eps
+        self.tabs = None if runner.tables is None else tuple(torch.empty_like(a) for a in runner.tables)
+        if self.tabs is not None:                       # (a capture-time launch reads them: valid entries from the start)
+            for dst, src in zip(self.tabs, runner.tables):
+                dst.copy_(src)
+        self.v = None if runner.v is None else self.tabs
         # (on the data form the update reads v itself, at the static t, from the static tables)
         self.veps = None if runner.v is None or plan.form == "data" else torch.empty((B, hw, Cc), device=dev)
         # scheduled guidance: this step's weight and the guided output
@@ -770,10 +850,19 @@ class _GraphedStep:
             upd.launch(st, img, read, hw, self.coef.data_ptr(), img, t=self.t, tables=self.v)
 
         def guided_step(st):
-            eng.launch(st)
+            out = eng.eps_nhwc
+            if self.sag:
+                # one stream, no branches: o, the mass and the degraded image, o~ on the same engine, the pair's second half
+                eng.launch(st, self._inputs)
+                runner.sag_degrade(eng, img, self.t, self.pair, self.x_deg, self.mass, st, self.tabs, self.taps)
+                eng.launch(st, self._inputs_deg)
+                self.pair[B:].copy_(eng.eps_nhwc.reshape(B, hw, Cc))        # (on the capturing stream: the current one)
+                out = self.pair
+            else:
+                eng.launch(st)
             if self.scheduled:
-                return tail(st, _Read.guided(runner.guide(eng.eps_nhwc, plan.mode, self.w, B, Cc, hw, self.g, st), B, Cc))
-            tail(st, _Read(eng.eps_nhwc, plan.mode, plan.weight, B, Cc))
+                return tail(st, _Read.guided(runner.guide(out, plan.mode, self.w, B, Cc, hw, self.g, st), B, Cc))
+            tail(st, _Read(out, plan.mode, plan.weight, B, Cc))
 
         self.graph = None if self.distilled else self._capture(eng, guided_step, dev)
         self.eng1 = self.graph1 = self.u1 = None
@@ -783,11 +872,10 @@ class _GraphedStep:
             eng1 = self.eng1 = eng if self.distilled else m._engine(B, img.shape[2], img.shape[3], eng.prec, runner.head(Cc))
             self.u1 = torch.zeros(B, device=dev) if runner.cond_only_mask() else None
             self.mask1 = torch.zeros(B, dtype=torch.bool, device=dev) if runner.cond_only_mask() else None
-            eng1.prepare(img, self.t, self.cond, self.layout, self.mask1)
-            self._inputs1 = eng1._keep_inputs
+            self._inputs1 = eng1.prepare(img, self.t, self.cond, self.layout, self.mask1)
 
             def cond_step(st):
-                eng1.launch(st)
+                eng1.launch(st, self._inputs1)
                 tail(st, _Read.guided(eng1.eps_nhwc, B, Cc))
 
             self.graph1 = self._capture(eng1, cond_step, dev)
@@ -821,8 +909,8 @@ class _GraphedStep:
             self.cond.copy_(cond)
         if self.layout is not None:
             self.layout.copy_(layout)
-        if self.v is not None:
-            for dst, src in zip(self.v, v):
+        if self.tabs is not None:
+            for dst, src in zip(self.tabs, v):
                 dst.copy_(src)
         self.ts, self.tab = _t_rows(times, img.shape[0], img.device), tab.to(img.device)
         if self.scheduled:
@@ -836,6 +924,10 @@ class _GraphedStep:
         if not guided:
             if self.u1 is not None:
                 self.u1.uniform_(0, 1)                  # the B-long draw of forward(cond_drop_prob=p0); nothing is dropped
+        elif self.sag:
+            if self.has_mask:
+                self.us.uniform_(0, 1)                  # one B-long draw per evaluation, as the eager step's two _draw_mask
+                self.us.uniform_(0, 1)
         elif self.has_mask:
             self.u.uniform_(0, 1)                       # prob_mask_like (openaimodel.py:462-463): same RNG consumption
             torch.lt(self.u, self.p, out=self.mask)
@@ -1103,8 +1195,8 @@ class Schedule_DDPM(nn.Module):
         # buffers stand in for them
         direct = "sqrt_alphas_cumprod" not in sk
         plan = resolve_plan(sk, "native", _model_behind(denoise_sample_fn), dkw, T=timesteps, lv=lv,
-                            par="v" if direct and h.parameterization == "v" else None)
-        if direct and plan.par == "v":
+                            par=h.parameterization if direct else None, shape=shape)
+        if direct and (plan.par == "v" or plan.sag):
             sk = dict(sk, sqrt_alphas_cumprod=self.sqrt_alphas_cumprod,
                       sqrt_one_minus_alphas_cumprod=self.sqrt_one_minus_alphas_cumprod)
         order = kwargs.get("step_indices")          # bench / teacher-forced tests: visit only these steps (rows of the chain)
@@ -1197,9 +1289,9 @@ class DDIMSampler(object):
         loop = self.ddim_sampling if self.sampler_type == "ddim" else self.plms_sampling
         return loop(shape, sampling_kwargs=sampling_kwargs, ac_visited=visited, **kwargs)
 
-    def _plan(self, sk, denoise_sample_fn, dkw, ac_visited):
+    def _plan(self, sk, denoise_sample_fn, dkw, ac_visited, shape=None):
         return resolve_plan(sk, self.sampler_type, _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps,
-                            ac_visited=ac_visited)
+                            ac_visited=ac_visited, shape=shape)
 
     @torch.no_grad()
     def plms_sampling(self, shape, sampling_kwargs, denoise_sample_fn_kwargs=None, denoise_sample_fn=None, ac_visited=None,
@@ -1211,7 +1303,7 @@ class DDIMSampler(object):
         sk = sampling_kwargs
         dev = torch.device(self.device)
         dkw = denoise_sample_fn_kwargs or {}
-        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)
+        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited, shape)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
@@ -1261,7 +1353,7 @@ class DDIMSampler(object):
         sk = sampling_kwargs
         dev = torch.device(self.device)
         dkw = dict(denoise_sample_fn_kwargs or {})
-        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)
+        plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited, shape)
         img = _start_image(shape, kwargs.get("x_T"), dev)
         vis = sk.get("vis")
         vis_noise = kwargs.get("vis_noise")                     # tests: the start noise a `vis` branch would draw
@@ -1294,7 +1386,7 @@ class DDIMSampler(object):
             dkw["layout"] = dkw["layout"][:ns].repeat_interleave(nw, 0)
             assert len(cs) == len(img) == len(dkw["layout"])
             dkw["cond_scale"] = cs
-            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)          # a tensor weight: no longer the fused step
+            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited, shape)          # a tensor weight: no longer the fused step
         if should_vis("chainvis"):
             # conditional / unconditional chain pairs from the same start noise (ddim_plms_sampler.py:157-175)
             ns = vis.chainvis_c.samples
@@ -1302,7 +1394,7 @@ class DDIMSampler(object):
             dkw["cond"] = dkw["cond"][:ns].repeat_interleave(2, 0)
             assert len(dkw["cond"]) == len(img)
             dkw["p0"] = torch.tensor([1, 0], device=dev, dtype=torch.float32).repeat(ns)
-            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited)          # p0: likewise
+            plan = self._plan(sk, denoise_sample_fn, dkw, ac_visited, shape)          # p0: likewise
         shape = tuple(img.shape)
         noise_fn = kwargs.get("noise_fn")
         total = self.ddim_timesteps.shape[0]
@@ -1397,9 +1489,11 @@ class PNDM_Sampler(object):
         sk = sampling_kwargs
         dkw = denoise_sample_fn_kwargs or {}
         # (its own schedule: no zero alphas_cumprod of the model's to visit)
-        plan = resolve_plan(sk, "pndm", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps)
+        plan = resolve_plan(sk, "pndm", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps, shape=shape)
         n = sk["num_timesteps"]
         times, tab = self.plan(n)
+        if plan.sag and plan.par == "eps":          # SAG forms x0 = (x - s1 eps) / sa from the TRAINING schedule at these times
+            plan.visits(sk["alphas_cumprod"].detach().float().cpu().numpy()[np.asarray(times, dtype=np.int64)])
         if n > 250:
             warnings.warn("according to the PNDM paper, most gains can be reaped when timestep<250, so it is not "
                           "meaningful to set a timestep larger than 250")
@@ -1504,7 +1598,7 @@ class DPMSolverSampler(object):
         if sk.get("dtp", 1) < 1.0:
             raise ValueError("dpmsolver: dynamic thresholding (dtp < 1) is not implemented for this sampler")
         dkw = denoise_sample_fn_kwargs or {}
-        plan = resolve_plan(sk, "dpmsolver", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps)
+        plan = resolve_plan(sk, "dpmsolver", _model_behind(denoise_sample_fn), dkw, T=self.ddpm_num_timesteps, shape=shape)
         ts, tab = self.plan(sk, plan.form)          # (the table, and its times with it, is built for the form)
         plan.visits(sk["alphas_cumprod"].detach().float().cpu().numpy()[ts])
         dev = torch.device(self.device)
@@ -1635,9 +1729,11 @@ class LatentDiffusion(nn.Module):
         sk.update(dict(alphas_cumprod=self.sampler.alphas_cumprod,
                        alphas_cumprod_prev=self.sampler.alphas_cumprod_prev, betas=self.sampler.betas,
                        parameterization=self.hparams.parameterization))
-        if self.hparams.parameterization == "v":        # the tables the v -> eps pass gathers from: the training schedule's
+        # the tables the v -> eps pass, and self-attention guidance in every parameterization, gather from: the training schedule's
+        if self.hparams.parameterization == "v" or sk.get("sag_scale"):
             sk.update(dict(sqrt_alphas_cumprod=self.sampler.sqrt_alphas_cumprod,
                            sqrt_one_minus_alphas_cumprod=self.sampler.sqrt_one_minus_alphas_cumprod))
+        if self.hparams.parameterization == "v":
             # a zero-terminal-SNR schedule is sampled on the data form wherever there is one (plms / pndm stay on eps: plms
             # works as long as its spacing does not visit the last timestep, and is refused by the sampler when it does)
             # (the 'native' update of a learned-variance model has one form, whose 'v' row never divides by sa)

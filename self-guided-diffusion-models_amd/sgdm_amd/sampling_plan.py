@@ -12,7 +12,8 @@ import torch
 # the defaults of the sampling kwargs this module reads, each stated once (``clip_denoised`` has none: a sampler that clips
 # needs it; None: absent)
 DEFAULTS = dict(parameterization="eps", v_form="eps", cfg_rescale=0, cfg_interval=None, cfg_distilled=False, pag_scale=0,
-                pag_layers=None, pag_drop_cond=None, lv_native=False, native_steps=None, dtp=1, noise_dropout=0, hip_graph=True)
+                pag_layers=None, pag_drop_cond=None, sag_scale=0, sag_layer=None, sag_threshold=None, sag_blur_sigma=None,
+                lv_native=False, native_steps=None, dtp=1, noise_dropout=0, hip_graph=True)
 
 
 def _opt(sk, key):
@@ -109,6 +110,72 @@ def pag_options(sk, fused=True, model=None):
     return s, model._pag_set(tuple(sorted(set(want))), 2), bool(drop)
 
 
+SAG_DEFAULTS = dict(sag_layer="middle_block.1", sag_threshold=1.0, sag_blur_sigma=1.0)
+SAG_TAPS = 9                                        # the blur's kernel size, fixed (csrc/sag.hip)
+
+
+def _real(v):
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def sag_scale_option(sk):
+    """the sampling kwarg ``sag_scale`` (self-attention guidance, Hong et al. 2023): a finite number >= 0; 0, the default,
+    is off.  ValueError for anything else (a bool included).  Pure host code."""
+    s = _opt(sk, "sag_scale")
+    if not _real(s) or not 0.0 <= s < float("inf"):                                        # (NaN fails the comparison)
+        raise ValueError(f"sag_scale={s!r}: a finite number >= 0 (0: off)")
+    return float(s)
+
+
+def sag_options(sk, fused=True, model=None, shape=None):
+    """None (off), or ``(s, layer, psi, sigma)`` of the sampling kwargs ``sag_scale`` / ``sag_layer`` / ``sag_threshold`` /
+    ``sag_blur_sigma``: self-attention guidance, o + s (o - o~) with o the conditional evaluation at B and o~ the SAME network
+    on the image whose x0 prediction is blurred (9 taps, std ``sigma``, default 1.0) where the attention mass of ``layer``
+    (an attention-layer prefix of ``model``; default the middle block's, 'middle_block.1') exceeds ``psi`` (default 1.0), re-noised
+    -- the cfg form of the step kernels over the pair [o ; o~] with w := s, whatever the model's scale_type; ``cond_scale`` is
+    not read.  ValueError, before anything is loaded or launched, for a value out of range, an unknown ``sag_layer``, the three
+    other kwargs without ``sag_scale > 0``, ``pag_scale`` or ``cfg_distilled`` next to it, the learned-variance 'native' update, a
+    step that is not the drop-in UNet's fused one (``fused``: SamplingPlan.fused -- a generic denoise_sample_fn, p0, a tensor
+    cond_scale), a model whose attention is not the self-attention block (unetca_fast, use_spatial_transformer) and an image
+    (``shape``, when the caller knows it) with a side below 5: the reflection pad of the blur must be smaller than the side.
+    Pure host code: no device, no library."""
+    sk = sk or {}
+    s = sag_scale_option(sk)
+    given = {k: _opt(sk, k) for k in SAG_DEFAULTS}
+    if s == 0:
+        if any(v is not None for v in given.values()):
+            raise ValueError("sag_layer / sag_threshold / sag_blur_sigma without sag_scale > 0")
+        return None
+    if pag_scale_option(sk) > 0:
+        raise ValueError("sag_scale with pag_scale: each forms the second half of the guided step its own way; stacking them "
+                         "would need three evaluations")
+    if cfg_distilled_option(sk):
+        raise ValueError("sag_scale with cfg_distilled: a distilled student has one (conditional) evaluation per step, there "
+                         "is no second half to guide with")
+    if _opt(sk, "lv_native"):
+        raise ValueError("sag_scale with the learned-variance 'native' update: the degraded image is formed from the mean "
+                         "prediction alone; not implemented")
+    if not fused or model is None:
+        raise ValueError("sag_scale needs the fused step: the drop-in UNet's forward_with_cond_scale as denoise_sample_fn, no "
+                         "p0 and no tensor cond_scale")
+    if model.KIND == "unetca_fast":
+        raise ValueError("self-attention guidance is not defined for unetca_fast: its Attention_LR keys are "
+                         "[context | null | self], the map is not one over the image")
+    if getattr(model, "use_spatial_transformer", False):
+        raise ValueError("self-attention guidance is not implemented for use_spatial_transformer")
+    layer, psi, sigma = (SAG_DEFAULTS[k] if v is None else v for k, v in given.items())
+    known = model.attention_prefixes()
+    if not isinstance(layer, str) or layer not in known:
+        raise ValueError(f"sag_layer={layer!r}: one attention-layer prefix out of {known}")
+    for name, v in (("sag_threshold", psi), ("sag_blur_sigma", sigma)):
+        if not _real(v) or not 0.0 < v < float("inf"):
+            raise ValueError(f"{name}={v!r}: a finite number > 0")
+    if shape is not None and min(int(shape[-2]), int(shape[-1])) <= SAG_TAPS // 2:
+        raise ValueError(f"sag_scale on a {int(shape[-2])}x{int(shape[-1])} image: the {SAG_TAPS}-tap blur reflects "
+                         f"{SAG_TAPS // 2} pixels at the border, every side must be at least {SAG_TAPS // 2 + 1}")
+    return s, layer, float(psi), float(sigma)
+
+
 V_FORM_SAMPLERS = ("native", "ddim", "dpmsolver")
 
 
@@ -197,7 +264,7 @@ def _fused(model, kw, distilled, pag_on):
     w = kw.get("cond_scale")
     if distilled:                                   # the same step with its conditional evaluation alone, whatever the weight
         return model is not None and kw.get("p0") is None
-    if pag_on:                                      # the doubled evaluation whatever the weight: cond_scale is not read
+    if pag_on:                                      # PAG's doubled evaluation, SAG's pair, whatever the weight: cond_scale is not read
         return model is not None and kw.get("p0") is None and not isinstance(w, torch.Tensor)
     if model is None or not isinstance(w, (int, float)) or kw.get("p0") is not None:
         return False
@@ -236,8 +303,12 @@ class SamplingPlan:
     clip: int                       # kwarg ``clip_denoised`` (no default), as the kernels take it; 'pndm': 0
     hip_graph: bool                 # kwarg ``hip_graph`` and SGDM_HIP_GRAPH != 0: the step may be captured
     fused: bool                     # the step kernels form the guided score from the engine's output (_fused)
-    mode: Optional[int]             # fused: how they read a doubled evaluation -- the model's form; 2 (cfg) under PAG
-    weight: Optional[float]         # fused: the weight of a guided evaluation -- cond_scale; pag_scale under PAG
+    mode: Optional[int]             # fused: how they read a doubled evaluation -- the model's form; 2 (cfg) under PAG / SAG
+    weight: Optional[float]         # fused: the weight of a guided evaluation -- cond_scale; pag_scale / sag_scale under PAG / SAG
+    # kwargs ``sag_scale`` / ``sag_layer`` / ``sag_threshold`` / ``sag_blur_sigma`` (sag_options): None, or (s, layer, psi, sigma) --
+    # a guided evaluation is TWO dependent evaluations at B, the second on the image degraded where ``layer`` attends, and the
+    # pair is read in the cfg form with weight s
+    sag: Optional[tuple] = None
 
     @property
     def layers(self):
@@ -265,18 +336,21 @@ class SamplingPlan:
         scheduled step reads its weight from the device, so a sweep over weights or intervals reuses one capture (whether
         an interval is requested stays: it adds the second graph); a static weight is a by-value kernel argument.  'v' on
         the eps form captures one more launch, the data form another update: three kinds.  PAG: the layer set chose the
-        engine, ``drop_cond`` the mask's probabilities."""
+        engine, ``drop_cond`` the mask's probabilities.  SAG: the layer names the tape buffers the capture reads, psi is a by-value
+        argument and sigma the content of the captured step's own taps."""
         w = None if self.scheduled or self.distilled else self.weight
         kind = "eps" if self.lv or self.par != "v" else "v/" + self.form
-        return (w, self.mode, kind, self.rescale, self.interval is not None, self.lv, self.distilled, self.pag and self.pag[1:])
+        return (w, self.mode, kind, self.rescale, self.interval is not None, self.lv, self.distilled, self.pag and self.pag[1:],
+                self.sag and self.sag[1:])
 
 
-def resolve_plan(sk, method=None, model=None, denoise_kwargs=None, T=None, ac_visited=None, lv=False, par=None):
+def resolve_plan(sk, method=None, model=None, denoise_kwargs=None, T=None, ac_visited=None, lv=False, par=None, shape=None):
     """the SamplingPlan of one trajectory, every refusal raised here: sampling kwargs ``sk``, the sampler's ``method`` name
     (None: a bare step runner, no sampler rules), the drop-in ``model`` behind the denoise function (None: a generic one), the
     denoise kwargs (``cond_scale``, ``p0``) and what only the sampler knows -- ``T`` training timesteps, ``ac_visited`` (the
     ``alphas_cumprod`` of the times it will visit; a sampler whose times follow from the plan calls ``plan.visits``), ``lv``
-    (the learned-variance 'native' update) and ``par`` (the schedule's parameterization, where the kwargs may leave it out)."""
+    (the learned-variance 'native' update), ``par`` (the schedule's parameterization, where the kwargs may leave it out) and ``shape``
+    (the image's, for the one refusal that reads it: sag_options)."""
     sk, kw = sk or {}, denoise_kwargs or {}
     par = sk.get("parameterization", par or DEFAULTS["parameterization"])
     lv = bool(lv or _opt(sk, "lv_native"))
@@ -287,16 +361,17 @@ def resolve_plan(sk, method=None, model=None, denoise_kwargs=None, T=None, ac_vi
             lv_native_option(sk)
         form = v_form_option(sk, method, ac_visited, par)
     distilled = cfg_distilled_option(sk)
-    fused = _fused(model, kw, distilled, pag_scale_option(sk) > 0)
+    fused = _fused(model, kw, distilled, pag_scale_option(sk) > 0 or sag_scale_option(sk) > 0)
     rescale, interval = cfg_options(dict(sk, lv_native=True) if lv else sk, fused)
     pag = pag_options(sk, fused, model)
+    sag = sag_options(dict(sk, lv_native=True) if lv else sk, fused, model, shape)
     mode = weight = None
     if fused:
-        mode = 2 if pag else model._scale_mode()
-        weight = pag[0] if pag else None if distilled else float(kw["cond_scale"])
+        mode = 2 if pag or sag else model._scale_mode()
+        weight = (pag or sag)[0] if pag or sag else None if distilled else float(kw["cond_scale"])
     return SamplingPlan(
         method=method, par=par, form=form, rescale=rescale, interval=interval, scheduled=rescale > 0 or interval is not None,
         distilled=distilled, pag=pag, lv=lv, native_steps=K, dtp=_opt(sk, "dtp"), noise_dropout=_opt(sk, "noise_dropout"),
         clip=0 if method in (None, "pndm") else 1 if sk["clip_denoised"] else 0,       # (PNDM never clips; the others need it)
         hip_graph=bool(_opt(sk, "hip_graph")) and os.environ.get("SGDM_HIP_GRAPH", "1") != "0",
-        fused=fused, mode=mode, weight=weight)
+        fused=fused, mode=mode, weight=weight, sag=sag)

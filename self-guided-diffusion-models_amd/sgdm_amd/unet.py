@@ -950,8 +950,8 @@ class _Engine:
 
     def prepare(self, x, t, cond, layout, mask, train=False):
         """host side of one evaluation: weight-pack refresh, dropout seeds, input validation / dtype normalisation.
-        The tensors are kept (``_keep_inputs``) and read by ``launch`` -- a captured launch sequence (hipGraph) re-reads
-        the SAME buffers on every replay, so a caller that replays must update them in place."""
+        The tensors are kept (``_keep_inputs``, also returned) and read by ``launch`` -- a captured launch sequence (hipGraph)
+        re-reads the SAME buffers on every replay, so a caller that replays must update them in place."""
         m, n = self.m, self.n
         stream = torch.cuda.current_stream().cuda_stream
         assert not (train and self.pag), "a perturbed-attention engine is inference only"
@@ -1005,11 +1005,14 @@ class _Engine:
                 assert cond.numel() == B * m._cond_width, (cond.shape, m._cond_width)
         self._keep_inputs = (x, t, cond, layout, mask_u8, B, is_i64, lfmt)
         self._train_mode = bool(train)               # the weight gradient of mlp_cond.0 reads the expanded rows
+        return self._keep_inputs
 
-    def launch(self, stream):
-        """device side: boundary kernels + the static launch program (no allocation, no sync: graph-capturable)"""
+    def launch(self, stream, inputs=None):
+        """device side: boundary kernels + the static launch program (no allocation, no sync: graph-capturable).  ``inputs``:
+        the prepared input set to read (what ``prepare`` returned; None: the last one) -- a capture that launches one engine
+        on several inputs (self-attention guidance: the image, then the degraded image) names each launch's own"""
         m, n, lib = self.m, self.n, self.lib
-        x, t, cond, layout, mask_u8, B, is_i64, lfmt = self._keep_inputs
+        x, t, cond, layout, mask_u8, B, is_i64, lfmt = self._keep_inputs if inputs is None else inputs
         cl = m._in_ch_total - m.in_channels
         L.check(lib.sgd_timestep_embedding(_ptr(t), _ptr(self.freqs), B, n, m.model_channels, _ptr(self.temb),
                                            stream), "temb")
