@@ -284,7 +284,9 @@ int sgd_stats_reduce(const float* partial, int32_t n, int32_t parts, int32_t c,
                      float* sums /* [n, c_total, 2] */, int32_t c_total, int32_t c_off, void* stream);
 /* sgd_stats_reduce of up to two concatenated sources (c = c0 + c1; partsX == 0: that source's sums are already in
  * `sums`, written by sgd_chan_stats) followed by sgd_gn_coef, in one launch.  `sums` is written for the sources with
- * partials (the training backward reads it); the coefficients are bit-identical to the two-launch route. */
+ * partials (the training backward reads it).  The partials are folded in double in strided groups, sgd_stats_reduce folds them
+ * in index order: sums and coefficients agree with the two-launch route to 1e-6 (max-rel), not bit for bit.  c0 + c1 <= 8192 and
+ * 24 bytes of LDS per channel from 512 channels on must fit 160 KB (c0 + c1 <= 6826), else SGD_ERR_ARG. */
 int sgd_gn_coef_parts(const float* partial0, int32_t parts0, int32_t c0, const float* partial1, int32_t parts1, int32_t c1,
                       float* sums, const float* gamma, const float* beta, const float* film, int32_t film_ld,
                       int32_t n, int32_t groups, int32_t hw, float eps, float* a, float* b, void* stream);
@@ -644,6 +646,8 @@ int sgd_colsum(const float* g, int32_t rows, int32_t c, int32_t ld, float* out, 
  *   gu may live at another resolution (ResBlock up/down, openaimodel.py:301-306): gu_mode SGD_RS_NONE same rows,
  *   SGD_RS_AVGPOOL2: forward pooled u 2x2 => gu is at 1/2 resolution, each x pixel receives gu/4;
  *   SGD_RS_UP2: forward upsampled u x2 => gu is at 2x resolution, each x pixel receives the sum of its 2x2 block.
+ *   Any other mode value, and SGD_RS_AVGPOOL2 with an odd h or w (the last row / column has no pooled gradient), is SGD_ERR_ARG,
+ *   nothing launched -- in sgd_gn_bwd_reduce for gu_mode, in sgd_gn_bwd_apply for gu_mode and, with gres non-NULL, gres_mode.
  * sgd_gn_bwd_reduce: S[n, c, 2] = (sum gpre, sum gpre * x) over the hw rows, gpre = gu * SiLU'(pre)      */
 int sgd_gn_bwd_reduce(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t c_total, int32_t c_off,
                       const float* a, const float* b, int32_t silu,
@@ -659,7 +663,8 @@ int sgd_gn_bwd_coef(const float* S, int32_t s_chunks, const float* sums, const f
                     float* A, float* B, float* Cc, float* dgamma_nc, float* dbeta_nc /* [n, c]: fold with sgd_colsum */,
                     float* dfilm, void* stream);
 /* dx[row, c_off + c] (+)= A*gu*SiLU'(a x + b) + B*x + C  (+ extra residual-path gradient gres, same gu_mode rules)
- * written into dst (row stride dst_ld, channel offset dst_off); accumulate: add to what is there. */
+ * written into dst (row stride dst_ld, channel offset dst_off); accumulate: add to what is there.  gu_mode and (gres non-NULL)
+ * gres_mode are checked as in sgd_gn_bwd_reduce: one of SGD_RS_NONE / AVGPOOL2 / UP2, AVGPOOL2 with even h and w only. */
 /* sgd_gn_bwd_coef + sgd_colsum_pair(dgamma_nc, dbeta_nc) in one launch (n <= 256, 8 * n * c / groups + 32 * n + 4 <= 64 KiB of LDS, else
  * SGD_ERR_ARG: use the two calls): A, B, Cc, dfilm as sgd_gn_bwd_coef; dgamma[c] / dbeta[c] (+)= scale * column sums over the
  * images, bit-identical to the two-call route. */

@@ -2063,6 +2063,13 @@ extern "C" int sgd_colsum_fold(const float* partial, int32_t chunks, int32_t c, 
     return sgd_check_launch();
 }
 
+// the resample modes fetch_g serves: same rows, the adjoint of a 2x2 average pool (whole 2x2 blocks only: with an odd h or w the
+// last row / column would read past the pooled gradient) and the adjoint of a nearest x2 upsample -- nothing else
+static bool gn_bwd_mode_ok(int mode, int h, int w) {
+    if (mode == SGD_RS_AVGPOOL2) return ((h | w) & 1) == 0;
+    return mode == SGD_RS_NONE || mode == SGD_RS_UP2;
+}
+
 extern "C" int sgd_gn_bwd_reduce(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t c_total,
                                  int32_t c_off, const float* a, const float* b, int32_t silu, const float* gu,
                                  int32_t gu_ld, int32_t gu_mode, float drop_p, uint32_t drop_seed, float* S,
@@ -2071,7 +2078,7 @@ extern "C" int sgd_gn_bwd_reduce(const float* x, int32_t n, int32_t h, int32_t w
     if (!x || !a || !b || !gu || !S || n <= 0 || h <= 0 || w <= 0 || c <= 0 || (c & 3) || (c_off & 3) ||
         c_off + c > c_total || (gu_ld & 3))
         return SGD_ERR_ARG;
-    if (gu_mode == SGD_RS_AVGPOOL2 && ((h | w) & 1)) return SGD_ERR_ARG;
+    if (!gn_bwd_mode_ok(gu_mode, h, w)) return SGD_ERR_ARG;
     hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(n * ((c + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x, h, w, c,
                        c_total, c_off, a, b, silu, gu, gu_ld, gu_mode, drop_p, drop_seed, S);
     return sgd_check_launch();
@@ -2150,6 +2157,7 @@ extern "C" int sgd_gn_bwd_apply(const float* x, int32_t n, int32_t h, int32_t w,
     if (!x || !a || !b || !gu || !A || !B || !Cc || !dst || n <= 0 || h <= 0 || w <= 0 || c <= 0 || (c & 3) ||
         (c_off & 3) || c_off + c > c_total || (gu_ld & 3) || (dst_ld & 3) || (dst_off & 3) || (gres && (gres_ld & 3)))
         return SGD_ERR_ARG;
+    if (!gn_bwd_mode_ok(gu_mode, h, w) || (gres && !gn_bwd_mode_ok(gres_mode, h, w))) return SGD_ERR_ARG;
     hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nblk((long)n * h * w * (c / 4), 65536)), dim3(256), 0,
                        (hipStream_t)stream, x, n, h, w, c, c_total, c_off, a, b, silu, gu, gu_ld, gu_mode, drop_p, drop_seed, A, B, Cc,
                        gres, gres_ld, gres_mode, dst, dst_ld, dst_off, accumulate);
